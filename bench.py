@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the commitment / proof hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    A plain run sets up, runs W warm-up steps and K timed steps of the headline workload and prints the JSON line (`value`,
+    `ms_per_step`); every object listed under "Extra objects" below is null there and is measured only with --full.
+    --dump-outputs DIR: after the timed steps, the commitments of the last timed step go to DIR as float .npy files (see dump_outputs).
     N > 1: either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...: RANK /
     WORLD_SIZE come from the environment), or bare -- `python bench.py --gpus N` with no WORLD_SIZE in the environment starts its own N
     ranks (one per GPU, torch.distributed.run on 127.0.0.1 with a free port) and prints their ONE JSON line.
@@ -13,7 +16,7 @@ library's own FromCompressedG1).  One step = one pass of the hot path over one b
 `batch` normalised commitments resident in HBM.  Blobs are independent, so ranks shard them with no data-path
 collective ("scaling": "weak"); value = commitments of all ranks / max-over-ranks time.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only):
   roofline      -- dominant kernel of the commitment step (k_fb_accumulate, the fixed-base table walk): algorithmic bytes per launch /
                    HIP-event launch time OF THE TIMED STEPS (launches_timed, launch_over_step <= 1.002 asserted) vs 8 TB/s, the PMC traffic of the committed
                    rocprofv3 passes (profiles/), and `mac`: the kernel's v_mad_u64_u32 rate against the rate MEASURED on this GPU in this run (kzg_hip_calibrate).
@@ -61,6 +64,25 @@ from benchlib.roofline import walk_roofline, walk_mac, issue_model  # noqa: E402
 from benchlib.launch import self_launch  # noqa: E402
 from benchlib.in_process import run_in_process_child, in_process_child  # noqa: E402
 
+DUMP_LIMIT_BYTES = 60 * 10**6        # --dump-outputs stays under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, rank, world, fs, commitments):
+    """What a caller of the timed path receives, exactly, as float arrays: `commitments` (B, 3, 12) float64 -- the library's result images
+    (Jacobian X, Y, Z of 6 Montgomery u64 limbs, Z = one) as little-endian 32-bit words -- and `commitments_compressed` (B, 48) float32, the
+    48-byte compressed encodings.  Rank r > 0 adds the suffix _rank<r>.  Beyond DUMP_LIMIT_BYTES over all ranks, a fixed seeded sample of
+    rows is written, its indices in `rows`."""
+    B = commitments.shape[0]
+    keep = max(1, DUMP_LIMIT_BYTES // (world * (3 * 12 * 8 + 48 * 4 + 8)))
+    rows = np.arange(B) if B <= keep else np.sort(np.random.default_rng(20260).choice(B, keep, replace=False))
+    pts = np.ascontiguousarray(commitments[rows])
+    sfx = "" if rank == 0 else "_rank%d" % rank
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "commitments%s.npy" % sfx), pts.view(np.uint32).astype(np.float64))
+    np.save(os.path.join(out_dir, "commitments_compressed%s.npy" % sfx), fs.to_compressed_g1(pts).astype(np.float32))
+    if len(rows) < B:
+        np.save(os.path.join(out_dir, "rows%s.npy" % sfx), rows.astype(np.float64))
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -78,6 +100,9 @@ def main():
     ap.add_argument("--fk20-4096-batch", type=int, default=512, help="polynomials per step of the fk20_4096 block (0: skip)")
     ap.add_argument("--no-in-process", action="store_true", help="skip the multi-device-handle leg (a child process at the end)")
     ap.add_argument("--in-process", action="store_true", help="(default) also time the multi-device handle of the C ABI over the job's devices: reported under in_process and rccl")
+    ap.add_argument("--full", action="store_true", help="also run every secondary leg: CPU baseline, self-checks, rooflines, sweeps, FK20, reference transforms, in_process "
+                                                        "(a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the commitments of the last timed step to DIR/<name>.npy (float64 / float32, exact)")
     ap.add_argument("--in-process-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--devices", type=str, default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -89,7 +114,7 @@ def main():
         sys.exit(self_launch(args.gpus))
     rank, world, local = dist_env()
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             base = cpu_baseline(float(os.environ.get("KZG_BENCH_CPU_BUDGET_S", "6")))   # first: the all-cores leg forks, which must precede HIP initialisation
         except Exception as e:                              # noqa: BLE001  (a missing / unbuildable oracle must not cost the GPU measurement)
@@ -118,26 +143,26 @@ def main():
     setup = fs.from_compressed_g1(raw)                      # 4096 x [1337^i]G1, decompressed on the device
     ks = kz.KZGSettings(fs, setup)
     ks.set_table_budget_gb(args.table_gb)                   # 110 GB = the library's default budget (c = 16 on 8 windows, 103 GB); table_sweep has the smaller ones
-    cal_mad, cal_add, cal_fpmul = fs.calibrate()            # measured on THIS GPU: v_mad_u64_u32 / v_add_u32 lane-ops/s, lazy F_p products/s
-    golden = os.path.join(ROOT, "tests", "golden")
-    pins = json.load(open(os.path.join(golden, "fk20_pins.json")))
-    pmc = {}
-    for name in ("r06_pmc.json", "r05_pmc.json", "r04_pmc.json", "r03_pmc.json", "r02_pmc.json", "r01_pmc_traffic.json"):   # counters of the committed rocprofv3 passes (tools/profile_round.sh)
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
-            pmc["_file"] = "profiles/" + name
-            break
-        except (OSError, ValueError):
-            continue
+    pmc, shapes, shapes_file = {}, [], None
+    if args.full:
+        cal_mad, cal_add, cal_fpmul = fs.calibrate()        # measured on THIS GPU: v_mad_u64_u32 / v_add_u32 lane-ops/s, lazy F_p products/s
+        golden = os.path.join(ROOT, "tests", "golden")
+        pins = json.load(open(os.path.join(golden, "fk20_pins.json")))
+        for name in ("r06_pmc.json", "r05_pmc.json", "r04_pmc.json", "r03_pmc.json", "r02_pmc.json", "r01_pmc_traffic.json"):   # counters of the committed rocprofv3 passes (tools/profile_round.sh)
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
+                pmc["_file"] = "profiles/" + name
+                break
+            except (OSError, ValueError):
+                continue
 
-    shapes, shapes_file = [], None
-    for name in ("r06_kernel_shapes.json", "r05_kernel_shapes.json", "r04_kernel_shapes.json"):                 # (kernel, grid, workgroup) rows of the committed rocprofv3 kernel trace (tools/rocprof_summary.py)
-        try:
-            shapes = json.load(open(os.path.join(ROOT, "profiles", name)))["rows"]
-            shapes_file = "profiles/" + name
-            break
-        except (OSError, ValueError, KeyError):
-            continue
+        for name in ("r06_kernel_shapes.json", "r05_kernel_shapes.json", "r04_kernel_shapes.json"):             # (kernel, grid, workgroup) rows of the committed rocprofv3 kernel trace (tools/rocprof_summary.py)
+            try:
+                shapes = json.load(open(os.path.join(ROOT, "profiles", name)))["rows"]
+                shapes_file = "profiles/" + name
+                break
+            except (OSError, ValueError, KeyError):
+                continue
 
     def profile_avg_ms(prefix, grid, wg):
         """average duration of the launches of that shape in the committed kernel trace (all kernels whose name starts with `prefix`)"""
@@ -177,10 +202,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    # self-check of the timed path before timing it: blob 0 of rank 0 is SURVEY.md vector F
+    # the first commitment builds the fixed-base table (set-up, not a step); --full: self-check of the timed path before timing it, blob 0 of
+    # rank 0 is SURVEY.md vector F
     step()
     torch.cuda.synchronize()
-    if rank == 0:
+    if args.full and rank == 0:
         c0 = d_out[0].cpu().numpy().view(np.uint64).reshape(1, 3, 6)
         hx = fs.to_compressed_g1(c0)[0].tobytes().hex()
         exp = json.load(open(os.path.join(ROOT, "tests", "golden", "derived_vectors.json")))["F_blob_seed1"]["commit_monomial_s1337"]
@@ -190,7 +216,7 @@ def main():
     tc_, tw_, tb_ = ks.table_info()   # every rank builds its own table; an allocation failure degrades to a smaller window (capi.hip)
     sys.stderr.write("[rank %d/%d, device %d] commitment table: %d-bit windows x %d, %.1f GB\n" % (rank, world, local, tc_, tw_, tb_ / 1e9))
     rccl = None
-    if use_dist:
+    if use_dist and args.full:
         # who is in the job: every rank contributes (rank, device index, table window bits, windows, table bytes) through the SAME
         # collective library the data path would use (one all-gather of 5 x int64); rank 0 reports what it saw
         mine = torch.tensor([rank, local, tc_, tw_, tb_], dtype=torch.int64, device="cuda")
@@ -202,16 +228,20 @@ def main():
                 "self_launched": bool(os.environ.get("KZG_BENCH_SELF_LAUNCHED")),
                 "tables_per_rank": [{"rank": r[0], "window_bits": r[2], "windows": r[3], "GB": r[4] / 1e9} for r in seen],
                 "all_gather_proofs_ms": None, "sharded_one_polynomial_ms": None}
-    # HIP events around every kernel of the TIMED steps (on the launch stream): the roofline's launch duration is taken from the very launches `value` is made of
-    secs = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, barrier, max_over_ranks, before_timed=lambda: lib.kzg_hip_prof_reset(fs.h, 1))
+    # --full: HIP events around every kernel of the TIMED steps (on the launch stream): the roofline's launch duration is taken from the very launches `value` is made of
+    secs = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, barrier, max_over_ranks,
+                       before_timed=(lambda: lib.kzg_hip_prof_reset(fs.h, 1)) if args.full else None)
     tot, cnt = C.c_double(0), C.c_uint64(0)
     dominant = b"fb_accumulate"
-    lib.kzg_hip_prof_read(fs.h, dominant, C.byref(tot), C.byref(cnt))
-    if not cnt.value:
-        dominant = b"msm_accumulate"
+    if args.full:
         lib.kzg_hip_prof_read(fs.h, dominant, C.byref(tot), C.byref(cnt))
-    lib.kzg_hip_prof_reset(fs.h, 0)
+        if not cnt.value:
+            dominant = b"msm_accumulate"
+            lib.kzg_hip_prof_read(fs.h, dominant, C.byref(tot), C.byref(cnt))
+        lib.kzg_hip_prof_reset(fs.h, 0)
     value = B * world * args.steps / secs
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, fs, d_out.cpu().numpy().view(np.uint64).reshape(B, 3, 6))
 
     def poly_lincomb(d_rows, stride, rho_h, count, n):
         """sum_c rho_c row_c over device-resident rows (bls.PolyLinComb's kernel), returned as host images"""
@@ -244,20 +274,22 @@ def main():
 
     # ALL outputs of the last timed step (the KAT above pins blob 0 only): sum_b rho_b C_b == CommitToPoly(sum_b rho_b blob_b) for random rho --
     # one B-term LinCombG1 over the step's outputs as caller-supplied points and one lone commitment (other launch shapes than the timed one)
-    rho_c = mont_blobs(0xC0FFEE + rank, 1, n=B)[0]
-    lhs_c = fs.lin_comb_g1(d_out.cpu().numpy().view(np.uint64).reshape(B, 3, 6), rho_c)
-    rhs_c = ks.commit_to_poly(poly_lincomb(d_blobs, N_COEFF, rho_c, B, N_COEFF))
-    if not all_ranks_ok(np.array_equal(lhs_c, rhs_c)):
-        raise SystemExit("bench self-check failed: sum_b rho_b C_b != CommitToPoly(sum_b rho_b blob_b) over the %d outputs of the timed step" % B)
-    self_check = {"rows_checked": B, "per_rank": True, "ranks": world,
-                  "method": "sum_b rho_b C_b == CommitToPoly(sum_b rho_b blob_b), rho random in F_r: one %d-term LinCombG1 over the step's outputs + one commitment; "
-                            "blob 0 also against SURVEY.md vector F" % B}
+    self_check = None
+    if args.full:
+        rho_c = mont_blobs(0xC0FFEE + rank, 1, n=B)[0]
+        lhs_c = fs.lin_comb_g1(d_out.cpu().numpy().view(np.uint64).reshape(B, 3, 6), rho_c)
+        rhs_c = ks.commit_to_poly(poly_lincomb(d_blobs, N_COEFF, rho_c, B, N_COEFF))
+        if not all_ranks_ok(np.array_equal(lhs_c, rhs_c)):
+            raise SystemExit("bench self-check failed: sum_b rho_b C_b != CommitToPoly(sum_b rho_b blob_b) over the %d outputs of the timed step" % B)
+        self_check = {"rows_checked": B, "per_rank": True, "ranks": world,
+                      "method": "sum_b rho_b C_b == CommitToPoly(sum_b rho_b blob_b), rho random in F_r: one %d-term LinCombG1 over the step's outputs + one commitment; "
+                                "blob 0 also against SURVEY.md vector F" % B}
 
     # SURVEY.md 8(d) config 2 also names the batch sizes 1, 64 and 1024: the same step at those sizes and at round 1's 512 (secondary
     # figures; the headline's step is `--batch` blobs: the end of a launch -- block trees, one inversion per blob -- is amortised over more
     # work the larger the step)
     batch_sweep = {}
-    if not args.no_fk20:
+    if args.full and not args.no_fk20:
         big = mont_blobs(1 + rank * 2048, 2048)
         d_big = torch.from_numpy(big.view(np.int64)).cuda()
         d_big_out = torch.zeros((2048, 18), dtype=torch.int64, device="cuda")
@@ -306,9 +338,9 @@ def main():
     table_sweep = drop_in = lincomb = latency = fk20 = roofline_fk20 = fk20m = ref_benches = fk20_4096 = roofline_fk20_4096 = roofline_fft_fr = roofline_das = None
     secondary_error = None
     try:
-        if os.environ.get("KZG_BENCH_FAIL_SECONDARY"):           # test hook (tests/test_bench_dist.py)
+        if args.full and os.environ.get("KZG_BENCH_FAIL_SECONDARY"):   # test hook (tests/test_bench_dist.py)
             raise RuntimeError("KZG_BENCH_FAIL_SECONDARY is set")
-        if not args.no_extras and not args.no_fk20 and world == 1:   # single-GPU characterisations: not repeated by every rank of an N > 1 run
+        if args.full and not args.no_extras and not args.no_fk20 and world == 1:   # single-GPU characterisations: not repeated by every rank of an N > 1 run
             # --- commitments/s against the HBM budget of the fixed-base table (library default: 110 GB -> c = 16 on 8 windows = 103 GB, the headline)
             table_sweep = {}
             for gb in (5.0, 9.0, 17.0, 60.0):
@@ -523,7 +555,7 @@ def main():
 
         fk20 = None
         roofline_fk20 = None
-        if not args.no_fk20:
+        if args.full and not args.no_fk20:
             fk = kz.FK20SingleSettings(ks, 4096)
             FB = args.fk20_batch
             polys_h = mont_blobs(4 + rank * FB, FB)[:, :2048, :].copy()
@@ -648,7 +680,7 @@ def main():
                     fk20["all_gather_proofs"] = {"error": "%s: %s" % (type(e).__name__, e)}
             fk.close()
 
-        if not args.no_fk20 and args.fk20_4096_batch > 0:
+        if args.full and not args.no_fk20 and args.fk20_4096_batch > 0:
             # The metric's literal input: a 4096-ELEMENT blob (BASELINE config 4b).  FK20Single (fk20_single.go:122-137) needs a domain of twice
             # the polynomial's length: scale 13, 8192-point setup [s^i]G1 of the reference's test secret (GenerateTestingSetup on the device).
             # Two forms on the same settings: FK20Single 4096 coefficients -> 4096 proofs (131 072 MulG1 in the reference, against 81 920 for
@@ -740,7 +772,7 @@ def main():
             fk13.close(); ks13.close(); fs13.close()
 
         fk20m = None
-        if not args.no_fk20 and args.fk20_multi_batch > 0:
+        if args.full and not args.no_fk20 and args.fk20_multi_batch > 0:
             # BASELINE config 5: FK20Multi, scale 16 (n2 = 65536, 32768 coefficients), chunk length 16 -> 4096 coset proofs per polynomial.
             # Setup [s^i]G1 for the reference's test secret is generated on the device (GenerateTestingSetup).
             s_test = 1927409816240961209460912649124
@@ -799,7 +831,7 @@ def main():
             fkm.close(); ks16.close(); fs16.close()
 
         ref_benches = None
-        if not args.no_fk20:
+        if args.full and not args.no_fk20:
             # The three transforms the reference publishes numbers for (BENCH.md, Kilic column, Ryzen 9 5950X, 1 thread), scale 12,
             # device-resident batches: FFT over F_r (:43), FFT over G1 (:55), DAS FFT extension (:31).
             def rate(fn, units, reps):
@@ -897,7 +929,7 @@ def main():
     fs.close()
     del d_blobs, d_out
     torch.cuda.empty_cache()
-    if not args.no_in_process and not args.no_fk20 and not os.environ.get("KZG_BENCH_FAIL_SECONDARY"):
+    if args.full and not args.no_in_process and not args.no_fk20 and not os.environ.get("KZG_BENCH_FAIL_SECONDARY"):
         barrier()                                             # every rank has released its tables
         if rank == 0:
             in_process = run_in_process_child(list(range(world)) if (world > 1 and torch.cuda.device_count() >= world) else [local])
@@ -939,7 +971,7 @@ def main():
             "metric": "KZG commitments/sec (CommitToPoly, 4096-element blob); FK20 half: value_fk20_4096", "value": value, "unit": "commitments/s",
             "value_fk20_4096": fk_half, "unit_fk20_4096": "all-proofs/s", "roofline_fk20_4096": roofline_fk20_4096,
             "cpu_baseline_fk20_4096": base.get("fk20_4096") if isinstance(base, dict) else None,
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": secs / args.steps * 1e3,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": secs / args.steps * 1e3, "full": args.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "dtype_note": "30/32-bit limbs in u32 lanes, 64-bit accumulators (v_mad_u64_u32): 381-bit F_p and 255-bit F_r Montgomery arithmetic",
             "data": "synthetic",
             "config": {"workload": "CommitToPoly, 4096-coeff blobs, eth/trusted_setup.json monomial setup (s=1337), %d blobs/step/GPU resident in HBM, fixed-base table budget %g GB (library default 110 GB: signed 16-bit windows, 8 of them walked by both GLV halves of every scalar, 103 GB; see table_sweep)" % (B, args.table_gb),

@@ -138,7 +138,7 @@ def test_bench_two_ranks_under_torch_distributed_run():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64", "--fk20-batch", "8", "--fk20-multi-batch", "2",
-           "--table-gb", "4", "--no-extras", "--fk20-4096-batch", "4", "--no-in-process"]
+           "--table-gb", "4", "--no-extras", "--fk20-4096-batch", "4", "--no-in-process", "--full"]
     # own session: on a timeout the whole process group (launcher + both ranks) is killed, nothing is left holding the device or the pipes
     import signal
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
@@ -175,7 +175,7 @@ def test_bench_self_launches_its_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(KZG_BENCH_BACKEND="gloo", KZG_HIP_FK20_FB_BUDGET_GB="3")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64", "--fk20-batch", "8",
-           "--fk20-multi-batch", "2", "--table-gb", "4", "--fk20-4096-batch", "4"]   # (with the in_process leg: rank 0 runs the child, rank 1 waits on the store)
+           "--fk20-multi-batch", "2", "--table-gb", "4", "--fk20-4096-batch", "4", "--full"]   # (with the in_process leg: rank 0 runs the child, rank 1 waits on the store)
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
     try:
         out, err = proc.communicate(timeout=600)
@@ -230,7 +230,7 @@ def test_bench_line_survives_a_failing_secondary_leg():
     import json
     import subprocess
     env = dict(os.environ, KZG_BENCH_FAIL_SECONDARY="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64", "--table-gb", "4", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64", "--table-gb", "4", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -238,6 +238,73 @@ def test_bench_line_survives_a_failing_secondary_leg():
     d = json.loads(lines[0])
     assert d["value"] > 0 and d["roofline"]["frac"] > 0 and d["roofline"]["mac"]["frac"] > 0
     assert "KZG_BENCH_FAIL_SECONDARY" in d["secondary_error"] and d["fk20"] is None
+
+
+P_MOD = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
+
+
+def _check_dumped_commitments(out, rows):
+    """the two arrays of --dump-outputs describe the same points: X of the library image (Montgomery, R = 2^384) is the x of the 48-byte
+    encoding, Z is one, and both survive the float round trip exactly"""
+    c, z = np.load(os.path.join(out, "commitments.npy")), np.load(os.path.join(out, "commitments_compressed.npy"))
+    assert c.dtype == np.float64 and c.shape == (rows, 3, 12) and z.dtype == np.float32 and z.shape == (rows, 48)
+    assert np.array_equal(c, np.floor(c)) and c.min() >= 0 and c.max() < 2 ** 32 and z.min() >= 0 and z.max() <= 255
+    r_inv = pow(1 << 384, -1, P_MOD)
+    for i in range(rows):
+        x_mont, z_mont = (sum(int(v) << (32 * k) for k, v in enumerate(c[i, j])) for j in (0, 2))
+        assert z_mont == (1 << 384) % P_MOD
+        assert x_mont * r_inv % P_MOD == int.from_bytes(bytes(z[i].astype(np.uint8)), "big") & ((1 << 381) - 1)
+    return z
+
+
+def test_dump_outputs_writes_exact_floats_and_caps_the_size(tmp_path):
+    """bench.dump_outputs on host data (oracle points): exact float images, file names per rank, a fixed seeded sample beyond the size cap"""
+    import bench
+    from oracle import koracle as ko
+
+    class HostFS:
+        to_compressed_g1 = staticmethod(ko.g1_compress)
+
+    pts = ko.g1_affine(np.stack([ko.g1_mul(ko.g1_generator(), ko.fr_from_ints([k])) for k in range(1, 9)]))
+    bench.dump_outputs(str(tmp_path / "a"), 0, 1, HostFS(), pts)
+    assert sorted(os.listdir(tmp_path / "a")) == ["commitments.npy", "commitments_compressed.npy"]
+    _check_dumped_commitments(str(tmp_path / "a"), 8)
+    many = np.ascontiguousarray(np.broadcast_to(pts, (50000, 8, 3, 6)).reshape(-1, 3, 6))      # 400 000 rows: over the cap at 4 ranks
+    sizes = []
+    for _ in range(2):
+        bench.dump_outputs(str(tmp_path / "b"), 3, 4, HostFS(), many)
+        rows = np.load(tmp_path / "b" / "rows_rank3.npy")
+        sizes.append(sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")))
+        assert len(rows) < len(many) and np.array_equal(rows, np.unique(rows))
+        c = np.load(tmp_path / "b" / "commitments_rank3.npy")
+        assert np.array_equal(c, many[rows.astype(np.int64)].view(np.uint32).astype(np.float64))
+    assert sizes[0] == sizes[1] and 4 * sizes[0] < 64 * 10 ** 6
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_the_timed_outputs(tmp_path):
+    """a plain run (no --full) times the headline step only: the contract's keys, null for every secondary object, value x ms_per_step = the
+    step's blobs; --dump-outputs holds the commitments of the last timed step, blob 0 (seed 1) is SURVEY.md vector F"""
+    import json
+    import subprocess
+    out = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "64", "--table-gb", "4", "--dump-outputs", out]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["unit"] == "commitments/s" and d["higher_is_better"] is True and d["dtype"] == "u32" and d["metric"].startswith("KZG commitments/sec")
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] * 1e-3 - 64) < 1e-6
+    for k in ("roofline", "cpu_baseline", "self_check", "rccl", "table_sweep", "drop_in", "lincomb", "latency", "fk20", "fk20_4096", "fk20_multi",
+              "reference_benchmarks", "in_process", "value_fk20_4096"):
+        assert d[k] is None, k
+    assert not d["batch_sweep"]
+    assert sorted(os.listdir(out)) == ["commitments.npy", "commitments_compressed.npy"]
+    z = _check_dumped_commitments(out, 64)
+    exp = json.load(open(os.path.join(ROOT, "tests", "golden", "derived_vectors.json")))["F_blob_seed1"]["commit_monomial_s1337"]
+    assert bytes(z[0].astype(np.uint8)).hex() == exp
 
 
 def _error_paths(obj, path=""):
@@ -289,13 +356,13 @@ def test_cpu_baseline_carries_no_swallowed_error():
 
 @pytest.mark.gpu
 def test_bench_line_has_no_failed_leg():
-    """the whole default bench (every leg, reduced sizes) on a box where everything should work: no leg may have swallowed an exception into an
+    """the whole --full bench (every leg, reduced sizes) on a box where everything should work: no leg may have swallowed an exception into an
     {"error": ...} object, `secondary_error` is null, and the dominant kernel's launches -- timed on the timed steps -- fit inside the steps"""
     import json
     import subprocess
     env = dict(os.environ, KZG_BENCH_CPU_BUDGET_S="0.5", KZG_HIP_FK20_FB_BUDGET_GB="8")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "512", "--table-gb", "9", "--fk20-batch", "16",
-           "--fk20-multi-batch", "2", "--fk20-4096-batch", "4"]
+           "--fk20-multi-batch", "2", "--fk20-4096-batch", "4", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]

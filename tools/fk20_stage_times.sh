@@ -3,7 +3,7 @@
 R=$(pwd); cd /tmp && export TMPDIR=/tmp
 for mode in fast wnaf; do
   out=$R/gpurun_out/fkstage_$mode; rm -rf $out
-  KZG_HIP_G1_MUL=$mode KZG_HIP_FB_BUDGET_GB=10 rocprofv3 --kernel-trace --output-format csv -d $out -o t -- python $R/bench.py --steps 2 --warmup 0 --batch 8 --no-cpu-baseline --fk20-multi-batch 1 > /dev/null 2>&1
+  KZG_HIP_G1_MUL=$mode KZG_HIP_FB_BUDGET_GB=10 rocprofv3 --kernel-trace --output-format csv -d $out -o t -- python $R/bench.py --full --steps 2 --warmup 0 --batch 8 --no-cpu-baseline --fk20-multi-batch 1 > /dev/null 2>&1
   f=$(find $out -name "*kernel_trace.csv" | head -1)
   python - "$f" $mode <<'PY'
 import csv, sys

@@ -4,7 +4,7 @@
 R=$(pwd); cd /tmp && export TMPDIR=/tmp
 for b in ${1:-8 32 64 256 1024}; do
   out=$R/gpurun_out/fkstage_b$b; rm -rf $out
-  KZG_HIP_FB_BUDGET_GB=10 rocprofv3 --kernel-trace --output-format csv -d $out -o t -- python $R/bench.py --steps 2 --warmup 1 --batch 64 --no-cpu-baseline --no-extras --fk20-multi-batch 0 --fk20-batch $b > /dev/null 2>&1
+  KZG_HIP_FB_BUDGET_GB=10 rocprofv3 --kernel-trace --output-format csv -d $out -o t -- python $R/bench.py --full --steps 2 --warmup 1 --batch 64 --no-cpu-baseline --no-extras --fk20-multi-batch 0 --fk20-batch $b > /dev/null 2>&1
   f=$(find $out -name "*kernel_trace.csv" | head -1)
   python - "$f" $b <<'PY'
 import csv, sys

@@ -2,7 +2,7 @@
 # kernel-by-kernel timeline of ONE DAUsingFK20 batch (scale 12) at the bench's batch size
 R=$(pwd); cd /tmp && export TMPDIR=/tmp
 out=$R/gpurun_out/fk20trace; rm -rf $out
-KZG_HIP_FB_BUDGET_GB=4 rocprofv3 --kernel-trace --output-format csv -d $out -o t -- python $R/bench.py --steps 2 --warmup 0 --batch 8 --no-cpu-baseline --fk20-multi-batch 0 > /dev/null 2>&1
+KZG_HIP_FB_BUDGET_GB=4 rocprofv3 --kernel-trace --output-format csv -d $out -o t -- python $R/bench.py --full --steps 2 --warmup 0 --batch 8 --no-cpu-baseline --fk20-multi-batch 0 > /dev/null 2>&1
 python - "$(find $out -name '*kernel_trace.csv' | head -1)" <<'PY'
 import csv, sys, collections
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))

@@ -57,9 +57,9 @@ rows, the regular odd-digit schedule on the same table where wavefronts straddle
 two decimation-in-frequency stages of the inverse transform ({L} stage launches per step).
 
 Commands (GPU box): `bash tools/profile_round2.sh r02` =
-`cd /tmp && rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras` (summary by
+`cd /tmp && rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras` (summary by
 `tools/rocprof_summary.py`), then ONE `rocprofv3 --pmc <counter> --kernel-trace --output-format csv` pass per counter and per kernel
-(`bench.py --no-fk20` for `k_fb_accumulate`: every launch 512 blobs; `bench.py --no-extras --fk20-multi-batch 0` for the stage kernels
+(`bench.py --full --no-fk20` for `k_fb_accumulate`: every launch 512 blobs; `bench.py --full --no-extras --fk20-multi-batch 0` for the stage kernels
 `k_g1_fft_stage` / `k_g1_fft_stage_dif`, launches of the 512-polynomial FK20 step selected by grid size), then the un-profiled bench line;
 `tools/make_r02_profiles.py` writes this file and `r02_pmc.json`.  `k_fb_build_*`, `k_msm_window_rows`, `k_g1_to_affine`,
 `k_g1_fixed_base_powers`, `k_g1_decompress` are one-time settings construction; `k_cal_*` is the in-run calibration.

@@ -50,7 +50,7 @@ for k in ("k_g1_fft_stage",):
     e["valu_insts_per_step"] = e["valu_insts_per_launch"] * L
 json.dump(pm, open(os.path.join(R, "profiles", "r03_pmc.json"), "w"), indent=1)
 ks = open(os.path.join(src, "kernel_stats.md")).read()
-hdr = ("# r03 -- kernel trace of `python bench.py --no-cpu-baseline` at its default step sizes (rocprofv3 --kernel-trace --stats, tools/profile_round3.sh), 1x MI355X\n\n"
+hdr = ("# r03 -- kernel trace of `python bench.py --full --no-cpu-baseline` at its default step sizes (rocprofv3 --kernel-trace --stats, tools/profile_round3.sh), 1x MI355X\n\n"
        "Un-profiled line of the same build on the same box: %.0f commitments/s (%.2f ms per 4096-blob step), FK20 %.0f all-proofs/s, FFT_Fr %.2f M/s, DAS extension %.2f M/s.\n\n"
        % (bl["value"], bl["ms_per_step"], bl["fk20"]["value"], bl["reference_benchmarks"]["fft_fr_scale12_per_s"]["value"] / 1e6,
           bl["reference_benchmarks"]["das_fft_extension_scale12_per_s"]["value"] / 1e6))

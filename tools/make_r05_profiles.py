@@ -60,7 +60,7 @@ def kernel_stats(trace_dir):
     rows_ = json.load(open(os.path.join(src_, "kernel_shapes.json")))["rows"]
     r_ = [x for x in rows_ if x["kernel"].startswith("k_fb_accumulate") and x["grid"] == 1048576 and x["workgroup"] == 256][0]
     avg = r_["avg_us"] / 1e3
-    hdr = """# r05 -- kernel trace of `python bench.py --no-cpu-baseline --no-extras --no-in-process` at its default step sizes (rocprofv3 --kernel-trace --stats, tools/profile_round5.sh), 1x MI355X
+    hdr = """# r05 -- kernel trace of `python bench.py --full --no-cpu-baseline --no-extras --no-in-process` at its default step sizes (rocprofv3 --kernel-trace --stats, tools/profile_round5.sh), 1x MI355X
 
 One row per LAUNCH SHAPE (kernel, grid, workgroup) -- tools/rocprof_summary.py; `r05_kernel_shapes.json` holds the same rows for bench.py, which prints the
 row of the launch it puts on its roofline line as `roofline.profile_avg_ms` beside its own HIP-event figure.
@@ -78,7 +78,7 @@ Profiled line: %d commitments/s (%.2f ms per 4096-blob step), FK20 %d all-proofs
        t_["fk20_4096"]["value"], d_["value"], d_["ms_per_step"], d_["fk20"]["value"], d_["fk20_4096"]["value"],
        d_["reference_benchmarks"]["fft_fr_scale12_per_s"]["value"] / 1e6, d_["reference_benchmarks"]["das_fft_extension_scale12_per_s"]["value"] / 1e6)
     open(os.path.join(R, "profiles", "r05_kernel_stats.md"), "w").write(hdr + open(os.path.join(src_, "kernel_stats.md")).read())
-    json.dump({"source": "rocprofv3 --kernel-trace --stats of `python bench.py --no-cpu-baseline --no-extras --no-in-process` (tools/profile_round5.sh); one row per (kernel, grid, workgroup)",
+    json.dump({"source": "rocprofv3 --kernel-trace --stats of `python bench.py --full --no-cpu-baseline --no-extras --no-in-process` (tools/profile_round5.sh); one row per (kernel, grid, workgroup)",
                "rows": rows_}, open(os.path.join(R, "profiles", "r05_kernel_shapes.json"), "w"), indent=0)
     print("kernel stats ok: k_fb_accumulate %.2f ms" % avg)
 

@@ -3,10 +3,10 @@
 # summary whose k_fb_accumulate average must agree with roofline.avg_launch_ms of the un-profiled line.  usage (GPU box): bash tools/profile_default_bench.sh
 R=$(pwd); out=$R/gpurun_out/prof_default; rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $out/trace -o def -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $out/trace_bench.json 2> $out/trace_err.txt
+rocprofv3 --kernel-trace --stats -d $out/trace -o def -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $out/trace_bench.json 2> $out/trace_err.txt
 db=$(find $out/trace -name "*.db" | head -1)
 python $R/tools/rocprof_summary.py $db $out/kernel_stats.md > /dev/null
-cd $R && python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $out/bench_line.json
+cd $R && python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $out/bench_line.json
 rm -rf $out/trace/*/*.db
 python - <<'PY'
 import json

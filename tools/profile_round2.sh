@@ -5,9 +5,9 @@
 tag=${1:-r02}
 R=$(pwd); out=$R/gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-BENCH_FK="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --fk20-multi-batch 0 --fk20-batch 512"   # FK20 step: 512 polynomials
-BENCH_FB="python $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-fk20 --batch 512"                               # commitment step only: every launch has 512 blobs
-rocprofv3 --kernel-trace --stats -d $out/trace -o $tag -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --batch 512 --fk20-batch 512 --fk20-multi-batch 256 > $out/trace_bench.json 2> $out/trace_err.txt
+BENCH_FK="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --fk20-multi-batch 0 --fk20-batch 512"   # FK20 step: 512 polynomials
+BENCH_FB="python $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-fk20 --batch 512"                               # commitment step only: every launch has 512 blobs
+rocprofv3 --kernel-trace --stats -d $out/trace -o $tag -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --batch 512 --fk20-batch 512 --fk20-multi-batch 256 > $out/trace_bench.json 2> $out/trace_err.txt
 db=$(find $out/trace -name "*.db" | head -1)
 python $R/tools/rocprof_summary.py $db $out/kernel_stats.md > /dev/null
 for ctr in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_WAVES; do
@@ -35,7 +35,7 @@ PY
  done
 done
 # the un-profiled line at the SAME launch shapes as the counter passes (512 blobs / 512 polynomials per step; bench.py's defaults are larger)
-cd $R && python bench.py --steps 10 --warmup 3 --batch 512 --fk20-batch 512 --fk20-multi-batch 256 2>/dev/null | tail -1 > $out/bench_line.json
+cd $R && python bench.py --full --steps 10 --warmup 3 --batch 512 --fk20-batch 512 --fk20-multi-batch 256 2>/dev/null | tail -1 > $out/bench_line.json
 rm -rf $out/trace/*/*.db $out/pmc_*/*agent_info.csv $out/pmc_*/*kernel_trace.csv $out/pmc_*/*counter_collection.csv 2>/dev/null
 cat $out/pmc_rows.jsonl
 du -sh $out

@@ -8,11 +8,11 @@
 tag=${1:-r03}
 R=$(pwd); out=$R/gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-CMD_FB="python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fk20"
-CMD_FK="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --fk20-multi-batch 0 --batch 512"
+CMD_FB="python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-fk20"
+CMD_FK="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --fk20-multi-batch 0 --batch 512"
 CMD_FR="env KZG_FR_PROBE_NO_AB=1 python $R/tools/fr_probe.py 1024"
 if [ -z "$SKIP_TRACE" ]; then
-rocprofv3 --kernel-trace --stats -d $out/trace -o $tag -- python $R/bench.py --no-cpu-baseline > $out/trace_bench.json 2> $out/trace_err.txt
+rocprofv3 --kernel-trace --stats -d $out/trace -o $tag -- python $R/bench.py --full --no-cpu-baseline > $out/trace_bench.json 2> $out/trace_err.txt
 db=$(find $out/trace -name "*.db" | head -1)
 python $R/tools/rocprof_summary.py $db $out/kernel_stats.md > /dev/null
 fi
@@ -31,6 +31,6 @@ for pass in "$P1" "$P2" "$P3" "$P4"; do
   rm -rf $d
  done
 done
-cd $R && python bench.py 2>/dev/null | tail -1 > $out/bench_line.json
+cd $R && python bench.py --full 2>/dev/null | tail -1 > $out/bench_line.json
 rm -rf $out/trace/*/*.db 2>/dev/null
 wc -l $out/pmc_rows.jsonl; du -sh $out

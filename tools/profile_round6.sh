@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 passes behind profiles/r06_*, at the launch shapes bench.py TIMES by default (4096-blob commitment step, 1024-polynomial FK20
 # step, 512-polynomial FK20 step on 4096-element blobs, 1024 F_r transforms per launch):
-#   (1) kernel trace of `bench.py --no-cpu-baseline --no-extras --no-in-process` (no table sweep: every k_fb_accumulate launch of 4096 workgroups
+#   (1) kernel trace of `bench.py --full --no-cpu-baseline --no-extras --no-in-process` (no table sweep: every k_fb_accumulate launch of 4096 workgroups
 #       walks the headline's 16-bit-window table (8 windows walked by both GLV halves, 103 GB)), summarised PER LAUNCH SHAPE (kernel, grid, workgroup) by tools/rocprof_summary.py:
 #       kernel_stats.md + kernel_shapes.json -- bench.py reads the latter (roofline.profile_avg_ms);
 #   (2) unless SKIP_PMC is set: counter passes (no other trace domain than --kernel-trace) over three commands:
@@ -11,11 +11,11 @@
 tag=${1:-r06}
 R=$(pwd); out=$R/gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-CMD_FB="python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fk20 --no-in-process"
-CMD_FK="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-in-process --fk20-multi-batch 0 --fk20-4096-batch 0 --batch 512"
+CMD_FB="python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-fk20 --no-in-process"
+CMD_FK="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-in-process --fk20-multi-batch 0 --fk20-4096-batch 0 --batch 512"
 CMD_FR="env KZG_FR_PROBE_NO_AB=1 python $R/tools/fr_probe.py 1024"
 if [ -z "$SKIP_TRACE" ]; then
-rocprofv3 --kernel-trace --stats -d $out/trace -o $tag -- python $R/bench.py --no-cpu-baseline --no-extras --no-in-process > $out/trace_bench.json 2> $out/trace_err.txt
+rocprofv3 --kernel-trace --stats -d $out/trace -o $tag -- python $R/bench.py --full --no-cpu-baseline --no-extras --no-in-process > $out/trace_bench.json 2> $out/trace_err.txt
 db=$(find $out/trace -name "*.db" | head -1)
 python $R/tools/rocprof_summary.py $db $out/kernel_stats.md $out/kernel_shapes.json > /dev/null
 fi
@@ -36,6 +36,6 @@ for pass in "$P1" "$P2" "$P3" "$P4"; do
  done
 done
 fi
-cd $R && python bench.py --no-in-process 2>/dev/null | tail -1 > $out/bench_line.json
+cd $R && python bench.py --full --no-in-process 2>/dev/null | tail -1 > $out/bench_line.json
 rm -rf $out/trace/*/*.db 2>/dev/null
 [ -f $out/pmc_rows.jsonl ] && wc -l $out/pmc_rows.jsonl; du -sh $out
