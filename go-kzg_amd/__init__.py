@@ -93,6 +93,11 @@ def lib():
         "kzg_hip_compute_proof_single_batch_dev": (i32, [vp, vp, u64, u64, vp, vp, vp]),
         "kzg_hip_compute_proof_multi": (i32, [vp, vp, u64, u64, u64, vp]),
         "kzg_hip_check_proof_multi_interpolation": (i32, [vp, vp, u64, vp, vp, vp]),
+        "kzg_hip_g2_from_compressed": (i32, [vp, vp, u64, vp]), "kzg_hip_pairings_verify_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
+        "kzg_hip_kzg_set_secret_g2": (i32, [vp, vp, u64]), "kzg_hip_check_proof_single_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
+        "kzg_hip_check_proof_multi_batch": (i32, [vp, vp, vp, vp, vp, u64, u64, vp]),
+        "kzg_hip_eth_set_setup_g2": (i32, [vp, vp, u64]), "kzg_hip_eth_verify_kzg_proof_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
+        "kzg_hip_pairing_test": (i32, [vp, vp, vp, u64, vp]),
         "kzg_hip_toeplitz_part2": (i32, [vp, vp, vp, u64, vp]), "kzg_hip_toeplitz_part3": (i32, [vp, vp, u64, vp]),
         "kzg_hip_fk20_single_settings_new": (i32, [vp, u64, pp]), "kzg_hip_fk20_single_settings_free": (None, [vp]),
         "kzg_hip_fk20_single_x_ext_fft": (i32, [vp, vp]), "kzg_hip_fk20_single": (i32, [vp, vp, u64, vp]),
@@ -204,6 +209,15 @@ def _fr(a):
 def _g1(a):
     a = np.ascontiguousarray(a, dtype=np.uint64)
     return a.reshape(-1, 3, 6)
+
+
+def _g2(a):
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    return a.reshape(-1, 3, 2, 6)
+
+
+def g2_empty(n):
+    return np.zeros((n, 3, 2, 6), dtype=np.uint64)
 
 
 def fr_empty(n):
@@ -365,6 +379,31 @@ class FFTSettings:
         out = g1_empty(data.shape[0])
         _chk(lib().kzg_hip_g1_from_compressed(self.h, _p(data), data.shape[0], _p(out)))
         return out
+
+    def g2_from_compressed(self, data):
+        """bls.FromCompressedG2 over (n, 96) uint8 ZCash encodings -> (n, 3, 2, 6) Kilic G2 images; KzgPanic(ERR_BAD_POINT) if any is invalid"""
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1, 96)
+        out = g2_empty(data.shape[0])
+        _chk(lib().kzg_hip_g2_from_compressed(self.h, _p(data), data.shape[0], _p(out)))
+        return out
+
+    def pairings_verify_batch(self, a1, a2, b1, b2):
+        """bls.PairingsVerify over rows: ok[i] = e(a1[i], a2[i]) == e(b1[i], b2[i])"""
+        a1, b1, a2, b2 = _g1(a1), _g1(b1), _g2(a2), _g2(b2)
+        n = a1.shape[0]
+        if not (b1.shape[0] == a2.shape[0] == b2.shape[0] == n):
+            raise KzgError(ERR_LEN_MISMATCH, "one point of each kind per check")
+        ok = np.zeros(n, dtype=np.uint8)
+        _chk(lib().kzg_hip_pairings_verify_batch(self.h, _p(a1), _p(a2), _p(b1), _p(b2), n, _p(ok)))
+        return ok.astype(bool)
+
+    def pairing_test(self, g1, g2):
+        """test hook: e(g1[i], g2[i])^(3 (p^12 - 1) / r) as 12 standard-form F_p integers per pair (memory order of the tower)"""
+        g1, g2 = _g1(g1), _g2(g2)
+        n = g1.shape[0]
+        out = np.zeros((n, 12, 6), dtype=np.uint64)
+        _chk(lib().kzg_hip_pairing_test(self.h, _p(g1), _p(g2), n, _p(out)))
+        return [[sum(int(v[k][i]) << (64 * i) for i in range(6)) for k in range(12)] for v in out]
 
     def g1_marshal_text(self, points):
         """bls.G1Point.MarshalText over a slice (bls/bls_all.go:20-22): lower-case hex of the 48-byte compressed form"""
@@ -540,6 +579,35 @@ class KZGSettings:
         out, xp = g1_empty(1), fr_empty(1)
         _chk(lib().kzg_hip_check_proof_multi_interpolation(self.h, _p(ys), ys.shape[0], _p(x), _p(out), _p(xp)))
         return out[0], xp[0]
+
+    def set_secret_g2(self, secret_g2):
+        """KZGSettings.SecretG2 (kzg.go:11-19): (n, 3, 2, 6) G2 images, n >= 2"""
+        g2 = _g2(secret_g2)
+        _chk(lib().kzg_hip_kzg_set_secret_g2(self.h, _p(g2), g2.shape[0]))
+
+    def check_proof_single_batch(self, commitments, proofs, xs, ys):
+        """KZGSettings.CheckProofSingle (kzg_single_proofs.go:57-70) over rows -> bool mask"""
+        c, pi, xs, ys = _g1(commitments), _g1(proofs), _fr(xs), _fr(ys)
+        n = c.shape[0]
+        if not (pi.shape[0] == xs.shape[0] == ys.shape[0] == n):
+            raise KzgError(ERR_LEN_MISMATCH, "one commitment, proof, x and y per check")
+        ok = np.zeros(n, dtype=np.uint8)
+        _chk(lib().kzg_hip_check_proof_single_batch(self.h, _p(c), _p(pi), _p(xs), _p(ys), n, _p(ok)))
+        return ok.astype(bool)
+
+    def check_proof_multi_batch(self, commitments, proofs, xs, ys):
+        """KZGSettings.CheckProofMulti (kzg_multi_proofs.go:47-75) over rows; ys is (count, n, 4) -> bool mask"""
+        c, pi, xs = _g1(commitments), _g1(proofs), _fr(xs)
+        count = c.shape[0]
+        ys = np.ascontiguousarray(ys, dtype=np.uint64)
+        ys = ys if ys.ndim == 3 else ys.reshape(count, -1, 4)
+        if ys.shape[0] != count or ys.shape[2] != 4:
+            raise KzgError(ERR_LEN_MISMATCH, "one row of ys per check")
+        if not (pi.shape[0] == xs.shape[0] == count):
+            raise KzgError(ERR_LEN_MISMATCH, "one commitment, proof and x per check")
+        ok = np.zeros(count, dtype=np.uint8)
+        _chk(lib().kzg_hip_check_proof_multi_batch(self.h, _p(c), _p(pi), _p(xs), _p(ys), ys.shape[1], count, _p(ok)))
+        return ok.astype(bool)
 
     def toeplitz_part2(self, toeplitz_coeffs, x_ext_fft):
         toeplitz_coeffs, x_ext_fft = _fr(toeplitz_coeffs), _g1(x_ext_fft)
@@ -889,6 +957,25 @@ class EthSettings:
         out, ys, ok = np.zeros((b, 48), dtype=np.uint8), fr_empty(b), np.zeros(b, dtype=np.uint8)
         _chk(lib().kzg_hip_eth_compute_kzg_proof_batch(self.h, _p(polys), self.n, b, _p(zs), _p(out), _p(ys), _p(ok)))
         return out, ys, ok.astype(bool)
+
+    def set_setup_g2(self, setup_g2):
+        """kzgSetupG2 (eth/globals.go:47): (n, 3, 2, 6) G2 images, n >= 2"""
+        g2 = _g2(setup_g2)
+        _chk(lib().kzg_hip_eth_set_setup_g2(self.h, _p(g2), g2.shape[0]))
+
+    def verify_kzg_proof_batch(self, commitments, zs, ys, proofs):
+        """eth.VerifyKZGProof (eth/eth.go:114-135) over rows of bytes: (count, 48) commitments, (count, 32) little-endian z and y, (count, 48) proofs
+        -> uint8 codes: 1 valid, 0 the pairing check failed, 2 z or y not below r, 3 commitment or proof not a valid G1 encoding"""
+        c = np.ascontiguousarray(commitments, dtype=np.uint8).reshape(-1, 48)
+        pi = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, 48)
+        zs = np.ascontiguousarray(zs, dtype=np.uint8).reshape(-1, 32)
+        ys = np.ascontiguousarray(ys, dtype=np.uint8).reshape(-1, 32)
+        n = c.shape[0]
+        if not (pi.shape[0] == zs.shape[0] == ys.shape[0] == n):
+            raise KzgError(ERR_LEN_MISMATCH, "one commitment, z, y and proof per check")
+        out = np.zeros(n, dtype=np.uint8)
+        _chk(lib().kzg_hip_eth_verify_kzg_proof_batch(self.h, _p(c), _p(zs), _p(ys), _p(pi), n, _p(out)))
+        return out
 
     def evaluate_polynomial_in_evaluation_form(self, polynomial, x):
         """eth.EvaluatePolynomialInEvaluationForm (eth/helpers.go:207-211)"""

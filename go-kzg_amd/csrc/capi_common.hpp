@@ -75,6 +75,7 @@ struct kzg_hip_fft {
     std::mutex pool_mu; std::condition_variable pool_cv; std::vector<pool_slot> pool_idle; int pool_total = 0;
     struct lincomb_promo *promo = nullptr;   // kzg_hip_lincomb_g1's memory of recent caller-supplied point sets (capi_core.hip); created on first use
 };
+struct g2_state;   // capi_verify.hip: the G2 points a handle verifies against
 struct kzg_hip_kzg {
     kzg_hip_fft *fs = nullptr;
     uint64_t n_setup = 0;
@@ -87,6 +88,8 @@ struct kzg_hip_kzg {
     hipStream_t copy_stream = nullptr;   // uploads of the host-buffer batch entry point, overlapped with the walk of the previous chunk
     hipEvent_t copy_done[2] = {nullptr, nullptr};
     std::unique_ptr<coalescer> co_commit, co_proof;   // merge concurrent one-polynomial calls into batched launches (coalesce.hpp)
+    std::shared_ptr<g2_state> g2;  // kzg_hip_kzg_set_secret_g2: SecretG2 and its prepared points (capi_verify.hip); a check holds its own reference
+    std::mutex g2_mu;              // guards the pointer `g2` (not the state behind it)
     std::shared_mutex tab_mu;      // table lifetime: coalesced batches walk d_fixed outside the handle mutex (shared), kzg_hip_kzg_set_table_budget_gb frees it (unique)
 };
 struct fk20_core {
@@ -235,6 +238,8 @@ struct kzg_hip_eth {
     fr *d_domain = nullptr;        // DomainFr: w^bitrev(i) (eth/globals.go:61-66)
     std::unique_ptr<coalescer> co_blob;   // concurrent one-blob BlobToKZGCommitment calls (eth/eth.go:145-151) merge into batched launches
     std::unique_ptr<coalescer> co_proof;  // concurrent ComputeKZGProof calls (eth/helpers.go:179-203)
+    std::shared_ptr<g2_state> g2;         // kzg_hip_eth_set_setup_g2: kzgSetupG2 and its prepared points (capi_verify.hip)
+    std::mutex g2_mu;
 };
 
 // ---------------------------------------------------------------------------------------------------------

@@ -1061,4 +1061,62 @@ KZG_HD g1j g1_to_kilic(const g1j &p) {
     return o;
 }
 
+// ---------------------------------------------------------------------------------------------
+// bls.FromCompressedG1 (Kilic G1.FromCompressed, bls/bls_kilic.go:114-121): ZCash form, big-endian x, bit7 compressed, bit6 inf, bit5 y > (p-1)/2.
+// Shared by k_g1_decompress and the eth verifier (k_pairing.hip).  Returns false for a missing compression flag, a malformed infinity,
+// x >= p, an x with no point on the curve, or a point outside the subgroup; `o` is then inf.  Device-internal image.
+// ---------------------------------------------------------------------------------------------
+KZG_HD bool fp_std_gt_half(const fp &y) {   // standard-form y > (p - 1) / 2
+    for (int i = 11; i >= 0; i--) {
+        uint32_t h = (FpP::mod(i) >> 1) | (i < 11 ? FpP::mod(i + 1) << 31 : 0u);
+        if (y.l[i] > h) return true;
+        if (y.l[i] < h) return false;
+    }
+    return false;
+}
+KZG_HD bool fp_from_be48(fp &o, const uint8_t *b, bool mask_flags) {   // big-endian 48 bytes -> standard form; false when >= p
+    o = zero<FpP>();
+    for (int i = 0; i < 48; i++) {
+        uint32_t v = b[47 - i];
+        if (i == 47 && mask_flags) v &= 0x1f;
+        o.l[i >> 2] |= v << (8 * (i & 3));
+    }
+    for (int i = 11; i >= 0; i--) { uint32_t m = FpP::mod(i); if (o.l[i] < m) return true; if (o.l[i] > m) return false; }
+    return false;
+}
+KZG_HD bool g1_decompress(g1j &o, const uint8_t *b) {
+    const uint8_t f = b[0];
+    o = g1_inf();
+    if (!(f & 0x80)) return false;
+    if (f & 0x40) {
+        uint32_t rest = f & 0x3f;
+        for (int i = 1; i < 48; i++) rest |= b[i];
+        return rest == 0;
+    }
+    fp x;
+    if (!fp_from_be48(x, b, true)) return false;
+    const fp xm = to_mont<FpP>(x);
+    fp four = one<FpP>(); four = add(four, four); four = add(four, four);
+    const fp y2 = add(mul(sqr(xm), xm), four);
+    fp acc = one<FpP>();   // y = y2^((p + 1) / 4)
+    for (int i = 11; i >= 0; i--) {
+        const uint32_t lo = FpP::mod(i) + (i == 0 ? 1u : 0u);   // p + 1: low limb 0xffffaaab + 1, no carry
+        const uint32_t hi = (i < 11) ? FpP::mod(i + 1) : 0u;
+        const uint32_t e = (lo >> 2) | (hi << 30);
+        for (int bit = 31; bit >= 0; bit--) { acc = sqr(acc); if ((e >> bit) & 1u) acc = mul(acc, y2); }
+    }
+    if (!equal<FpP>(sqr(acc), y2)) return false;
+    if (fp_std_gt_half(from_mont<FpP>(acc)) != ((f & 0x20) != 0)) acc = neg<FpP>(acc);
+    g1j p; p.x = xm; p.y = acc; p.z = one<FpP>();
+    // subgroup check ("point is not on correct subgroup"): [r]P == inf.  Everything downstream (the GLV split phi(P) = lambda P, the "cannot
+    // happen for points of G1" fast paths) assumes membership, so it is enforced where points enter.  The windowed multiplication uses the
+    // complete addition.
+    fr rk;
+    for (int i = 0; i < 8; i++) rk.l[i] = FrP::mod(i);
+    g1j tbl[15];
+    if (!is_inf(g1_mul_windowed(p, rk, tbl))) return false;
+    o = p;
+    return true;
+}
+
 }  // namespace kzg

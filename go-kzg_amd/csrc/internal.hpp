@@ -135,6 +135,22 @@ void launch_fb_mul_vec_files(hipStream_t s, const g1a *table, uint64_t table_n, 
                              uint64_t cnt, uint64_t batch, g1j *out, bool glv = false);
 void launch_g1_sum_files(hipStream_t s, const g1j *tmp, uint64_t nfiles, uint64_t cnt, uint64_t batch, g1j *out);
 
+// ---------------- k_pairing.hip ----------------
+// verification (pairing.hpp): G2 images are Kilic's (g2.hpp g2j), prepared points hold the 68 line coefficients of the Miller loop
+struct g2j; struct g2_prepared;
+void launch_g2_from_compressed(hipStream_t s, const uint8_t *in96, g2j *out_kilic, uint64_t n, uint32_t *bad_flag);
+void launch_g2_prepare(hipStream_t s, const g2j *in_kilic, uint64_t n, g2_prepared *out);
+void launch_pairs_g1_from_kilic(hipStream_t s, const g1j *a1, const g1j *b1, uint64_t n, g1j *p0, g1j *p1);   // p0 = -a1, p1 = b1 (internal domain)
+// KZG checks: p0 = C - E + [b] pi, p1 = -pi with E = [y] G1 (ys != null) or es[i]; Kilic images / Kilic-Montgomery scalars in
+void launch_kzg_check_inputs(hipStream_t s, const g1j *c, const g1j *pi, const fr *ys, const g1j *es, const fr *bs, uint64_t n, g1j *p0, g1j *p1);
+// CheckProofMulti's coset scaling over `count` rows of np values: row b times x_b^-i, xpow_n[b] = x_b^np
+void launch_fr_rows_scale_by_inv_powers(hipStream_t s, fr *c, uint64_t np, const fr *xs, uint64_t count, fr *xpow_n);
+// eth.VerifyKZGProof's byte inputs: status 0 valid, 2 z or y >= r, 3 undecodable commitment / proof
+void launch_eth_check_inputs(hipStream_t s, const uint8_t *c48, const uint8_t *zs, const uint8_t *ys, const uint8_t *pi48, uint64_t n, g1j *p0, g1j *p1, uint8_t *status);
+// ok[i] = e(p0[i], Q0) e(p1[i], Q1) == 1; shared_lines: Q0 = q0[0], Q1 = q1[0] for every check, else q0[i], q1[i]
+void launch_pairing_check(hipStream_t s, bool shared_lines, const g2_prepared *q0, const g2_prepared *q1, const g1j *p0, const g1j *p1, uint64_t n, uint8_t *ok);
+void launch_pairing_value(hipStream_t s, const g1j *g1_kilic, const g2_prepared *q, uint64_t n, fp *out);   // test hook: reduced e(g1[i], Q_i), standard form
+
 // profiling hook (HIP events around the dominant kernel), see capi.hip
 void prof_begin(hipStream_t s, const char *name);
 void prof_end(hipStream_t s, const char *name);

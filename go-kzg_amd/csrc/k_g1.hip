@@ -517,49 +517,9 @@ void launch_g1_compress(hipStream_t s, const g1j *in, uint8_t *out48, uint64_t n
 __global__ __launch_bounds__(G1_BLOCK, 2) void k_g1_decompress(const uint8_t *in48, g1j *out, uint64_t n, uint32_t *bad) {
     uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const uint8_t *b = in48 + 48 * t;
-    uint8_t f = b[0];
-    if (!(f & 0x80)) { atomicOr(bad, 1u); out[t] = g1_to_kilic(g1_inf()); return; }
-    if (f & 0x40) {
-        uint32_t rest = f & 0x3f;
-        for (int i = 1; i < 48; i++) rest |= b[i];
-        if (rest) atomicOr(bad, 1u);
-        out[t] = g1_to_kilic(g1_inf());
-        return;
-    }
-    fp x = zero<FpP>();
-    for (int i = 0; i < 48; i++) {
-        uint32_t v = b[47 - i];
-        if (i == 47) v &= 0x1f;
-        x.l[i >> 2] |= v << (8 * (i & 3));
-    }
-    // x < p
-    bool lt = false;
-    for (int i = 11; i >= 0; i--) { uint32_t m = FpP::mod(i); if (x.l[i] < m) { lt = true; break; } if (x.l[i] > m) break; }
-    if (!lt) { atomicOr(bad, 1u); out[t] = g1_to_kilic(g1_inf()); return; }
-    fp xm = to_mont<FpP>(x);
-    fp four = one<FpP>(); four = add(four, four); four = add(four, four);
-    fp y2 = add(mul(sqr(xm), xm), four);
-    // y = y2^((p + 1) / 4)
-    fp acc = one<FpP>();
-    for (int i = 11; i >= 0; i--) {
-        uint32_t lo = FpP::mod(i) + (i == 0 ? 1u : 0u);   // p + 1: low limb 0xffffaaab + 1, no carry
-        uint32_t hi = (i < 11) ? FpP::mod(i + 1) : 0u;
-        uint32_t e = (lo >> 2) | (hi << 30);
-        for (int bit = 31; bit >= 0; bit--) { acc = sqr(acc); if ((e >> bit) & 1u) acc = mul(acc, y2); }
-    }
-    if (!equal<FpP>(sqr(acc), y2)) { atomicOr(bad, 1u); out[t] = g1_to_kilic(g1_inf()); return; }
-    if (y_is_larger(from_mont<FpP>(acc)) != ((f & 0x20) != 0)) acc = neg<FpP>(acc);
-    g1j o; o.x = xm; o.y = acc; o.z = one<FpP>();
-    {   // subgroup check (Kilic G1.FromCompressed: "point is not on correct subgroup"): [r]P == inf.  Everything downstream (the GLV
-        // split phi(P) = lambda P, the "cannot happen for points of G1" fast paths) assumes membership, so it is enforced here, where
-        // points enter.  r in standard form as an 8-limb scalar; the windowed multiplication uses the complete addition.
-        fr rk;
-        for (int i = 0; i < 8; i++) rk.l[i] = FrP::mod(i);
-        g1j tbl[15];
-        if (!is_inf(g1_mul_windowed(o, rk, tbl))) { atomicOr(bad, 1u); out[t] = g1_to_kilic(g1_inf()); return; }
-    }
-    out[t] = g1_to_kilic(o);   // API output: Kilic image
+    g1j o;
+    if (!g1_decompress(o, in48 + 48 * t)) atomicOr(bad, 1u);
+    out[t] = g1_to_kilic(o);   // API output: Kilic image (inf for an invalid encoding)
 }
 void launch_g1_decompress(hipStream_t s, const uint8_t *in48, g1j *out, uint64_t n, uint32_t *bad_flag) {
     if (!n) return;

@@ -48,6 +48,9 @@ int kzg_hip_test_fr_inv(kzg_hip_fft *fs, const void *in_fr, uint64_t n, void *ou
 /* test hook: SHA-256 of a host buffer through the transcript's implementation (x86 SHA extensions or the portable loop; no device needed) */
 void kzg_hip_test_sha256(const void *data, uint64_t len, void *out32);
 
+/* test hook of the pairing (k_pairing.hip): out_fp12[i] = e(g1[i], g2[i]) raised to 3 (p^12 - 1) / r (the exponent of pairing.hpp's final
+ * exponentiation), 12 F_p elements of 48 bytes each in STANDARD form, order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1; G1 / G2 Kilic images in */
+int kzg_hip_pairing_test(kzg_hip_fft *fs, const void *g1, const void *g2, uint64_t n, void *out_fp12);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

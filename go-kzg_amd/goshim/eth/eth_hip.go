@@ -43,6 +43,9 @@ func initHip(lagrangeNaturalOrder []bls.G1Point) {
 
 // CloseHip releases the device side of the package (the Lagrange setup and its fixed-base table, up to 64 GB of HBM).
 func CloseHip() {
+	hipSetupG2Mu.Lock()
+	hipSetupG2For = nil // verify_hip.go: the next handle needs kzgSetupG2 again
+	hipSetupG2Mu.Unlock()
 	if hipEth != nil {
 		C.kzg_hip_eth_settings_free(hipEth)
 		hipEth = nil

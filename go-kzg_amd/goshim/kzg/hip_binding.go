@@ -60,6 +60,7 @@ func (ks *KZGSettings) CloseHip() {
 	hipMu.Lock()
 	h := hipKZG[uintptr(unsafe.Pointer(ks))]
 	delete(hipKZG, uintptr(unsafe.Pointer(ks)))
+	delete(hipSecretG2Set, uintptr(unsafe.Pointer(ks))) // verify_hip.go: the next handle needs SecretG2 again
 	hipMu.Unlock()
 	if h != nil {
 		C.kzg_hip_kzg_settings_free(h)

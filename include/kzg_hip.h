@@ -9,6 +9,8 @@
  *   Fr  : 32 B  = 4 x u64 little-endian limbs, Montgomery form (R = 2^256 mod r)      bls/bignum_kilic.go:21-23
  *   G1  : 144 B = 3 x 6 x u64 (X, Y, Z) Jacobian, Montgomery (R = 2^384 mod p), inf <=> Z == 0
  *                                                                                     bls/bls_kilic.go:30-35
+ *   G2  : 288 B = 3 x 2 x 6 x u64 (X, Y, Z) Jacobian over F_p2, each coordinate (c0, c1) Montgomery (R = 2^384 mod p),
+ *         inf <=> Z == 0                                                              bls/bls_kilic.go:57-62
  * Returned points are normalised: Z == R (affine) or Kilic's infinity image (0, R, 0), so that byte
  * comparison with any correct backend is meaningful.  Callers own all buffers; the library keeps no
  * caller pointer after a call returns (cgo rule).  All calls are blocking and thread-safe per handle.
@@ -240,6 +242,29 @@ int kzg_hip_eth_compute_aggregated_poly_and_commitment(kzg_hip_eth *eth, const v
 int kzg_hip_evaluate_poly_in_evaluation_form(kzg_hip_fft *fs, const void *poly_fr, uint64_t n, const void *x_fr, uint32_t scale, void *out_y_fr);
 /* eth.EvaluatePolynomialInEvaluationForm (eth/helpers.go:207-211): the same on DomainFr (bit-reversed order) */
 int kzg_hip_eth_evaluate_polynomial_in_evaluation_form(kzg_hip_eth *eth, const void *poly_fr, uint64_t n, const void *x_fr, void *out_y_fr);
+
+/* ---- verification (bls/bls_kilic.go:121-158, kzg_single_proofs.go:57, kzg_multi_proofs.go:47, eth/eth.go:114, eth/helpers.go:55) ----
+ * BATCH forms only: one lane per check (multi-Miller loop over two pairs + final exponentiation on the device).  Results are one byte per check.
+ * A check before its G2 setter is KZG_HIP_ERR_BAD_ARG; count == 0 is KZG_HIP_OK.
+ * kzg_hip_g2_from_compressed: bls.FromCompressedG2 over n 96-byte ZCash encodings -> n G2 images; KZG_HIP_ERR_BAD_POINT if ANY is invalid
+ * (flags, x >= p, not on the curve, not in the subgroup), like kzg_hip_g1_from_compressed. */
+int kzg_hip_g2_from_compressed(kzg_hip_fft *fs, const void *in96, uint64_t n, void *out_g2);
+/* bls.PairingsVerify over n checks: ok[i] = (e(a1[i], a2[i]) == e(b1[i], b2[i])); points at infinity contribute 1 (Kilic's AddPair) */
+int kzg_hip_pairings_verify_batch(kzg_hip_fft *fs, const void *a1_g1, const void *a2_g2, const void *b1_g1, const void *b2_g2, uint64_t n, uint8_t *ok);
+/* KZGSettings.SecretG2 (n >= 2 G2 images, copied): [1]G2 and [s]G2 are prepared at once, [s^n]G2 on the first multi check with n values */
+int kzg_hip_kzg_set_secret_g2(kzg_hip_kzg *ks, const void *secret_g2, uint64_t n);
+/* CheckProofSingle over `count` (commitment, proof, x, y): ok[i] = 1 when the proof verifies */
+int kzg_hip_check_proof_single_batch(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, uint64_t count,
+                                     uint8_t *ok);
+/* CheckProofMulti over `count` (commitment, proof, x, ys[i * n .. i * n + n)): needs SecretG2[n] (else KZG_HIP_ERR_LEN_MISMATCH) */
+int kzg_hip_check_proof_multi_batch(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, uint64_t n,
+                                    uint64_t count, uint8_t *ok);
+/* kzgSetupG2 (eth/globals.go:47): n >= 2 G2 images (kzg_hip_g2_from_compressed of setup_G2) */
+int kzg_hip_eth_set_setup_g2(kzg_hip_eth *eth, const void *setup_g2, uint64_t n);
+/* eth.VerifyKZGProof over `count` (commitment 48 B, z 32 B LE, y 32 B LE, proof 48 B): result[i] = 1 valid, 0 the pairing check failed,
+ * 2 z or y not below r ("invalid evaluation point" / "invalid expected output"), 3 commitment or proof not a valid G1 encoding */
+int kzg_hip_eth_verify_kzg_proof_batch(kzg_hip_eth *eth, const void *commitments48, const void *zs_le32, const void *ys_le32, const void *proofs48, uint64_t count,
+                                       uint8_t *result);
 /* ---- erasure recovery ----
  * FFTSettings.ZeroPolyViaMultiplication (zero_poly.go:116-217): vanishing polynomial of the missing indices of a size-`length`
  * domain; writes `length` evaluations and `length` coefficients (zero-padded).  No missing index -> all zeros (:117-119). */

@@ -19,6 +19,7 @@ namespace kzg {
 
 struct Fr { uint64_t l[4]; };                   // bls.Fr (bls/bignum_kilic.go:21-23)
 struct G1Point { uint64_t l[18]; };             // bls.G1Point (bls/bls_kilic.go:30-35)
+struct G2Point { uint64_t l[36]; };             // bls.G2Point (bls/bls_kilic.go:57-62): Jacobian over F_p2, Kilic images
 inline bool EqualFr(const Fr &a, const Fr &b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 inline bool EqualG1(const G1Point &a, const G1Point &b) { return std::memcmp(&a, &b, sizeof a) == 0; }   // outputs are normalised images
 
@@ -57,6 +58,22 @@ class FFTSettings {
     ~FFTSettings() { kzg_hip_fft_settings_free(h_); }
     FFTSettings(const FFTSettings &) = delete;
     FFTSettings &operator=(const FFTSettings &) = delete;
+    // bls.FromCompressedG2 over n 96-byte encodings; KZG_HIP_ERR_BAD_POINT if any is invalid
+    std::vector<G2Point> G2FromCompressed(const std::vector<std::array<uint8_t, 96>> &in) const {
+        std::vector<G2Point> out(in.size());
+        int st = kzg_hip_g2_from_compressed(h_, in.data(), in.size(), out.data());
+        if (st == KZG_HIP_ERR_BAD_POINT) throw Error(st, "invalid compressed G2 point");
+        detail::must(st);
+        return out;
+    }
+    // bls.PairingsVerify over rows (bls/bls_kilic.go:153-158)
+    std::vector<bool> PairingsVerifyBatch(const std::vector<G1Point> &a1, const std::vector<G2Point> &a2, const std::vector<G1Point> &b1,
+                                          const std::vector<G2Point> &b2) const {
+        std::vector<uint8_t> ok(a1.size());
+        if (a2.size() != ok.size() || b1.size() != ok.size() || b2.size() != ok.size()) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "slice lengths");
+        detail::must(kzg_hip_pairings_verify_batch(h_, a1.data(), a2.data(), b1.data(), b2.data(), ok.size(), ok.data()));
+        return std::vector<bool>(ok.begin(), ok.end());
+    }
     kzg_hip_fft *handle() const { return h_; }
 
     std::vector<Fr> ExpandedRootsOfUnity() const { std::vector<Fr> r(MaxWidth + 1); detail::must(kzg_hip_fft_roots(h_, 0, r.data())); return r; }
@@ -155,6 +172,23 @@ class KZGSettings {
     }
     G1Point ComputeProofMulti(const std::vector<Fr> &poly, uint64_t x, uint64_t n) const {   // kzg_multi_proofs.go:13-43
         G1Point out; detail::must(kzg_hip_compute_proof_multi(h_, poly.data(), poly.size(), x, n, &out)); return out;
+    }
+    void SetSecretG2(const std::vector<G2Point> &secretG2) {                              // KZGSettings.SecretG2 (kzg.go:11-19)
+        detail::must(kzg_hip_kzg_set_secret_g2(h_, secretG2.data(), secretG2.size()));
+    }
+    std::vector<bool> CheckProofSingleBatch(const std::vector<G1Point> &commitments, const std::vector<G1Point> &proofs, const std::vector<Fr> &xs,
+                                            const std::vector<Fr> &ys) const {             // kzg_single_proofs.go:57-70, batched
+        std::vector<uint8_t> ok(commitments.size());
+        if (proofs.size() != ok.size() || xs.size() != ok.size() || ys.size() != ok.size()) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "slice lengths");
+        detail::must(kzg_hip_check_proof_single_batch(h_, commitments.data(), proofs.data(), xs.data(), ys.data(), ok.size(), ok.data()));
+        return std::vector<bool>(ok.begin(), ok.end());
+    }
+    std::vector<bool> CheckProofMultiBatch(const std::vector<G1Point> &commitments, const std::vector<G1Point> &proofs, const std::vector<Fr> &xs,
+                                           const std::vector<Fr> &ys, uint64_t n) const {  // kzg_multi_proofs.go:47-75, batched; ys: count x n
+        std::vector<uint8_t> ok(commitments.size());
+        if (proofs.size() != ok.size() || xs.size() != ok.size() || ys.size() != ok.size() * n) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "slice lengths");
+        detail::must(kzg_hip_check_proof_multi_batch(h_, commitments.data(), proofs.data(), xs.data(), ys.data(), n, ok.size(), ok.data()));
+        return std::vector<bool>(ok.begin(), ok.end());
     }
 
   private:
@@ -288,6 +322,17 @@ class Settings {
         if (st == KZG_HIP_ERR_LEN_MISMATCH) throw Error(st, "polynomial has invalid length");
         if (st == KZG_HIP_ERR_BAD_ARG) throw Error(st, "invalid z challenge");
         detail::must(st);
+        return out;
+    }
+    void SetSetupG2(const std::vector<G2Point> &setupG2) {                                        // kzgSetupG2 (eth/globals.go:47)
+        detail::must(kzg_hip_eth_set_setup_g2(h_, setupG2.data(), setupG2.size()));
+    }
+    // eth.VerifyKZGProof over rows (eth/eth.go:114-135): 1 valid, 0 pairing check failed, 2 z or y >= r, 3 undecodable commitment / proof
+    std::vector<uint8_t> VerifyKZGProofBatch(const std::vector<Bytes48> &commitments, const std::vector<std::array<uint8_t, 32>> &zs,
+                                             const std::vector<std::array<uint8_t, 32>> &ys, const std::vector<Bytes48> &proofs) const {
+        std::vector<uint8_t> out(commitments.size());
+        if (zs.size() != out.size() || ys.size() != out.size() || proofs.size() != out.size()) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "slice lengths");
+        detail::must(kzg_hip_eth_verify_kzg_proof_batch(h_, commitments.data(), zs.data(), ys.data(), proofs.data(), out.size(), out.data()));
         return out;
     }
     Fr EvaluatePolynomialInEvaluationForm(const std::vector<Fr> &poly, const Fr &x) const {       // eth/helpers.go:207-211
