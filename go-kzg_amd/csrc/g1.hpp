@@ -165,31 +165,7 @@ struct g1x_acc {
         // branch weights: the compiler lays the (never taken) generic path out of the straight line of the walk loop: +2.7 % measured
         if (KZG_UNLIKELY(is_inf(q))) return;
         if (KZG_UNLIKELY(inf)) { v = g1xq_from_affine(q); inf = false; return; }
-#ifdef KZG_AB_FAKE_AFFINE   // TIMING-ONLY A/B (wrong results): the multiply-adds of a BATCH-AFFINE addition whose shared inversion, prefix-product storage and
-        // result storage came for free -- the ceiling of that scheme for the walk (profiles/r05_batch_affine.md): prefix product (1M), two products to unwind
-        // the inverse of the denominator (2M), lambda (1M), x3 (1S), y3 (1M) = 5M + 1S against the 8M + 2S (one reduction saved) of the XYZZ mixed addition
-        {
-            const fq x2 = unpackq(q.x), y2 = unpackq(q.y);
-            const fq d = subq<12>(x2, v.x);
-            const fq pre = mulq(v.zz, d);
-            const fq invd = mulq(v.zzz, pre);
-            v.zzz = mulq(v.zzz, d);
-            const fq lam = mulq(subq<6>(y2, v.y), invd);
-            const fq x3 = subq<3>(subq<12>(sqrq(lam), v.x), x2);
-            v.y = subq<6>(mulq(lam, subq<12>(v.x, x3)), v.y);
-            v.zz = pre; v.x = x3;
-            return;
-        }
-#endif
-#ifdef KZG_AB_FAKE_UNPACK   // TIMING-ONLY A/B (wrong results): what the walk would cost if table entries arrived as 13 limbs (profiles/r04_walk_ab.md)
-        fq fx_, fy_;
-#pragma unroll
-        for (int i_ = 0; i_ < 12; i_++) { fx_.l[i_] = q.x.l[i_]; fy_.l[i_] = q.y.l[i_]; }
-        fx_.l[12] = q.x.l[0] >> 8; fy_.l[12] = q.y.l[0] >> 8;
-        if (KZG_LIKELY(g1x_madd_fast(v, fx_, fy_))) return;
-#else
         if (KZG_LIKELY(g1x_madd_fast(v, unpackq(q.x), unpackq(q.y)))) return;
-#endif
         g1x s = g1x_madd(g1xq_pack(v), q);          // P == Q or P == -Q: generic, complete formulas
         if (is_inf(s)) inf = true; else v = g1xq_unpack(s);
     }
@@ -782,18 +758,6 @@ template <bool INL = false> KZG_HD bool g1_wnaf_table_affine_coz(const g1jq &p0,
     }
     if (KZG_UNLIKELY(!ok)) return false;
     const fq beta_q = unpackq(glv_beta());
-#ifdef KZG_WNAF_TABLE_AFFINE                                // A/B builds: the table normalised to affine points of E with one inversion (round 2)
-    fq zi = unpackq(inv<FpP>(packq(z)));                       // 1 / Z_8
-#pragma nounroll
-    for (int i = 7; i >= 0; i--) {
-        fq zi2 = sqrq(zi);
-        tbl[i].x = mulq(tbl[i].x, zi2);
-        tbl[i].y = mulq(tbl[i].y, mulq(zi2, zi));
-        tbl[i].bx = mulq(tbl[i].x, beta_q);
-        if (i) zi = mulq(zi, dz[i - 1]);                       // 1 / Z_i = (1 / Z_{i+1}) d_i
-    }
-    zc = one_q;
-#else
     // No inversion: entry i sits at Z_{i+1} = Z_1 d_0 .. d_{i-1}; all are brought to the COMMON Z_8 (times (Z_8 / Z_{i+1})^2, ^3) and read as AFFINE
     // points of the isomorphic curve E': y^2 = x^3 + b Z_8^6 -- the doubling and mixed-addition formulas of an a = 0 curve do not contain b, and
     // (x, y) -> (beta x, y) is the same endomorphism there -- so the multiplication runs on E' unchanged and its result (X, Y, Z) is the point
@@ -810,7 +774,6 @@ template <bool INL = false> KZG_HD bool g1_wnaf_table_affine_coz(const g1jq &p0,
         tbl[i].bx = mulq(tbl[i].x, beta_q);
     }
     zc = z;
-#endif
     return true;
 }
 KZG_HD void g1_wnaf_table_affine(const g1j &p, g1aq *tbl, g1jq *jt) { g1_wnaf_table_affine_q(g1jq_unpack(p), tbl, jt); }
@@ -933,11 +896,7 @@ template <bool INL_DBL = false, bool INL_ADD = false> KZG_HD int g1_wnaf_loop_aq
 // order < 16, never in G1) -- the callers then take the generic path for the whole product.
 // zc: the factor the multiplication's result Z has to be multiplied with (the table lives on an isomorphic curve: g1_wnaf_table_affine_coz)
 KZG_HD bool g1_wnaf_table(const g1jq &pq, g1aq *tbl, fq *dz, fq &zc) {
-#ifdef KZG_WNAF_TABLE_NOINLINE                              // A/B builds: the chain's products as calls (-0.2 .. -0.6 % FK20 measured)
-    return g1_wnaf_table_affine_coz<false>(pq, tbl, dz, zc);
-#else
-    return g1_wnaf_table_affine_coz<true>(pq, tbl, dz, zc);
-#endif
+    return g1_wnaf_table_affine_coz<true>(pq, tbl, dz, zc);     // products inlined: as calls they measured -0.2 .. -0.6 % FK20
 }
 template <bool INL_DBL = false, bool INL_ADD = false> KZG_HD int g1_mul_glv_wnaf_aq_q(const g1jq &pq, const fr &kk, g1aq *tbl, fq *dz, int8_t *d1, int8_t *d2, int stride, g1jq &out, g1j &packed) {
     fq zc;

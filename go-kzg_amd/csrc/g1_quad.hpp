@@ -58,7 +58,7 @@ template <int L> __device__ __forceinline__ void coop_sqr2(uint32_t role, const 
     const fq mine = sqrq_inl(quad_sel2(role, a0, a1));
     p0 = quad_bcast<0, L>(mine); p1 = quad_bcast<1, L>(mine);
 }
-// p <- 2 p (dbl-2008-s-1, a = 0), bounds (X, Y, ZZ, ZZZ) <= (11, 5, 2, 2) in and out -- the levels of coop_xyzz_dbl (k_msm.hip):
+// p <- 2 p (dbl-2008-s-1, a = 0), bounds (X, Y, ZZ, ZZZ) <= (11, 5, 2, 2) in and out (derived at g1xq_dbl_lane, k_msm.hip), in dependency levels:
 //   U = 2 Y;  L1: V = U^2, XX = X^2;  M = 3 XX;  L2: W = U V, S = X V, ZZ' = V ZZ, MM = M^2;  X' = MM - 2 S;
 //   L3: T1 = M (S - X'), T2 = W Y, ZZZ' = W ZZZ;  Y' = T1 - T2
 template <int L = 4> __device__ __forceinline__ void quad_xyzz_dbl(g1xq &p, uint32_t role) {
@@ -90,7 +90,7 @@ template <int L = 4> __device__ __forceinline__ bool quad_xyzz_madd(g1xq &p, con
     p.x = x3; p.y = addq(t1, t2); p.zz = zz3; p.zzz = zzz3;
     return true;
 }
-// a <- a + b for two XYZZ points (add-2008-s), bounds as in g1xq_add_fast / coop_xyzz_add (k_msm.hip): both operands (11, 5, 2, 2), result the same.
+// a <- a + b for two XYZZ points (add-2008-s), bounds as in g1xq_add_fast (g1.hpp): both operands (11, 5, 2, 2), result the same.
 // Returns false (a untouched) when the operands are equal or opposite.
 //   L1: U1 = X1 ZZ2, U2 = X2 ZZ1, S1 = Y1 ZZZ2, S2 = Y2 ZZZ1;  P = U2 - U1 (5), R = S2 - S1 (5);  L2: PP = P^2, RR = R^2, ZZ12 = ZZ1 ZZ2, ZZZ12 = ZZZ1 ZZZ2;
 //   L3: PPP = P PP, Q = U1 PP, ZZ3 = ZZ12 PP;  X3 = RR - PPP - 2 Q (11);  L4: T1 = R (Q - X3), T2 = S1 PPP, ZZZ3 = ZZZ12 PPP;  Y3 = T1 - T2 (5)

@@ -41,33 +41,28 @@ __device__ __forceinline__ void fb_partial_load(const fb_partial &p, g1xq &v) {
 // ---------------------------------------------------------------------------------------------------------
 // Wave-level exchange for the reduction trees (the "wavefront shuffles" of the north star): lane i receives what lane i + DELTA of the
 // SAME wavefront holds -- DPP row shifts (v_mov_b32 row_shl) inside a row of 16 lanes, ds_bpermute_b32 (the LDS crossbar, no LDS memory)
-// across rows; 53 moves per lazy XYZZ point, no LDS round trip, no workgroup barrier.  ROW = true (tree levels: only lanes i < DELTA <= 32
-// use the result, so a DPP shift never has to leave its row of 16); ROW = false (scans: every lane i with i + DELTA < 64 uses it):
-// ds_bpermute at every distance.  Lanes whose source falls outside receive an unspecified value.
-// KZG_NO_WAVE_SHUFFLE restores the LDS + __syncthreads exchange of round 2 (A/B builds, profiles/r03_wave_shuffle_ab.md); the bucket
-// scan of k_msm_reduce keeps the LDS form by default (KZG_MSM_REDUCE_SHUFFLE selects the shuffle form: measured 3 % slower).
+// across rows; 53 moves per lazy XYZZ point, no LDS round trip, no workgroup barrier.  Tree levels only: lanes i < DELTA <= 32 use the
+// result, so a DPP shift never has to leave its row of 16.  Lanes whose source falls outside receive an unspecified value.
 // ---------------------------------------------------------------------------------------------------------
-template <uint32_t DELTA, bool ROW> __device__ __forceinline__ uint32_t lane_down(uint32_t v) {
-    if constexpr (ROW && DELTA < 16) return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x100 + DELTA, 0xf, 0xf, false);   // row_shl:DELTA
+template <uint32_t DELTA> __device__ __forceinline__ uint32_t lane_down(uint32_t v) {
+    if constexpr (DELTA < 16) return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x100 + DELTA, 0xf, 0xf, false);   // row_shl:DELTA
     else return (uint32_t)__builtin_amdgcn_ds_bpermute((int)((((threadIdx.x & 63u) + DELTA) & 63u) << 2), (int)v);
 }
-template <uint32_t DELTA, bool ROW> __device__ __forceinline__ void point_down(g1xq &o, uint32_t &oinf, const g1xq &v, uint32_t vinf) {
+template <uint32_t DELTA> __device__ __forceinline__ void point_down(g1xq &o, uint32_t &oinf, const g1xq &v, uint32_t vinf) {
 #pragma unroll
     for (int i = 0; i < 13; i++) {
-        o.x.l[i] = lane_down<DELTA, ROW>(v.x.l[i]); o.y.l[i] = lane_down<DELTA, ROW>(v.y.l[i]);
-        o.zz.l[i] = lane_down<DELTA, ROW>(v.zz.l[i]); o.zzz.l[i] = lane_down<DELTA, ROW>(v.zzz.l[i]);
+        o.x.l[i] = lane_down<DELTA>(v.x.l[i]); o.y.l[i] = lane_down<DELTA>(v.y.l[i]);
+        o.zz.l[i] = lane_down<DELTA>(v.zz.l[i]); o.zzz.l[i] = lane_down<DELTA>(v.zzz.l[i]);
     }
-    oinf = lane_down<DELTA, ROW>(vinf);
+    oinf = lane_down<DELTA>(vinf);
 }
-// off in {1, 2, 4, 8, 16, 32}; wave-uniform
-template <bool ROW = true> __device__ __forceinline__ void point_down_any(g1xq &o, uint32_t &oinf, const g1xq &v, uint32_t vinf, uint32_t off) {
+// off in {4, 8, 16, 32}; wave-uniform
+__device__ __forceinline__ void point_down_any(g1xq &o, uint32_t &oinf, const g1xq &v, uint32_t vinf, uint32_t off) {
     switch (off) {
-    case 1: point_down<1, ROW>(o, oinf, v, vinf); break;
-    case 2: point_down<2, ROW>(o, oinf, v, vinf); break;
-    case 4: point_down<4, ROW>(o, oinf, v, vinf); break;
-    case 8: point_down<8, ROW>(o, oinf, v, vinf); break;
-    case 16: point_down<16, ROW>(o, oinf, v, vinf); break;
-    default: point_down<32, ROW>(o, oinf, v, vinf); break;
+    case 4: point_down<4>(o, oinf, v, vinf); break;
+    case 8: point_down<8>(o, oinf, v, vinf); break;
+    case 16: point_down<16>(o, oinf, v, vinf); break;
+    default: point_down<32>(o, oinf, v, vinf); break;
     }
 }
 
@@ -293,7 +288,7 @@ __global__ __launch_bounds__(MSM_NB) void k_msm_reduce(uint8_t *ws, size_t per_b
     const fb_partial *buckets = (const fb_partial *)(ws + b * per_blob + buckets_off) + (uint64_t)g * MSM_NB;
     g1x_acc acc; acc.inf = buckets[d].inf != 0;
     if (!acc.inf) fb_partial_load(buckets[d], acc.v);
-#if defined(KZG_NO_WAVE_SHUFFLE) || !defined(KZG_MSM_REDUCE_SHUFFLE)   // measured: the shuffle form below is 3 % SLOWER for a lone LinCombG1 (profiles/r03_wave_shuffle_ab.md)
+    // exchange through LDS: a lane-shuffle form of the scan measured 3 % SLOWER for a lone LinCombG1 (profiles/r03_wave_shuffle_ab.md)
     fb_partial_store(buf[d], acc);
     __syncthreads();
 #pragma nounroll
@@ -313,37 +308,12 @@ __global__ __launch_bounds__(MSM_NB) void k_msm_reduce(uint8_t *ws, size_t per_b
         }
         __syncthreads();
     }
-#else
-    // The 128 buckets of a group sit on two wavefronts.  Suffix scan INSIDE each wavefront by lane shuffles (6 steps, no LDS, no barrier),
-    // then the lower wavefront adds the upper one's total (its lane 0) -- the one exchange through LDS; the tree sum likewise: 6 shuffle
-    // levels per wavefront, then lane 0 adds the other wavefront's sum.  16 dependent additions as before, 2 barriers instead of 42.
-    const uint32_t lane = d & 63u;
-    if (acc.inf) acc.v = g1xq_from_affine(g1a_inf());      // defined limbs for the shuffles
-#pragma nounroll
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        g1xq v; uint32_t vi;
-        point_down_any<false>(v, vi, acc.v, acc.inf ? 1u : 0u, off);
-        if (lane + off < 64) g1x_acc_merge(acc, v, vi != 0);
-    }
-    if (d == 64) fb_partial_store(buf[0], acc);            // T_64 = the sum of the upper 64 buckets
-    __syncthreads();
-    if (d < 64) { g1xq v; fb_partial_load(buf[0], v); g1x_acc_merge(acc, v, buf[0].inf != 0); }
-    // acc = T_d (suffix sums); the answer is their sum
-#pragma nounroll
-    for (uint32_t off = 32; off >= 1; off >>= 1) {
-        g1xq v; uint32_t vi;
-        point_down_any(v, vi, acc.v, acc.inf ? 1u : 0u, off);
-        if (lane < off) g1x_acc_merge(acc, v, vi != 0);
-    }
-    __syncthreads();                                       // buf[0] has been read by everyone
-    if (d == 64) fb_partial_store(buf[0], acc);
-    __syncthreads();
-    if (d == 0) { g1xq v; fb_partial_load(buf[0], v); g1x_acc_merge(acc, v, buf[0].inf != 0); }
-#endif
     if (d == 0) fb_partial_store(((fb_partial *)(ws + b * per_blob + gsum_off))[g], acc);
 }
 
-// p <- 2 p on one lane (dbl-2008-s-1, a = 0; the formulas and bounds of coop_xyzz_dbl below: (X, Y, ZZ, ZZZ) <= (11, 5, 2, 2) in and out)
+// p <- 2 p on one lane (dbl-2008-s-1, a = 0) on lazy limbs, bounds (X, Y, ZZ, ZZZ) <= (11, 5, 2, 2) in and out:
+//   U = 2 Y : 10;  V = U^2, XX = X^2 : 2 (100, 121 <= 600);  M = 3 XX : 6;  W = U V, S = X V, ZZ' = V ZZ, MM = M^2 : 2
+//   X' = MM - 2 S (M = 5) : 7;  T1 = M (S - X') (S - X' with M = 8 : 10, 60), T2 = W Y : 2;  Y' = T1 - T2 (M = 3) : 5;  ZZZ' = W ZZZ : 2
 __device__ __forceinline__ void g1xq_dbl_lane(g1xq &p) {
     const fq u = addq(p.y, p.y);
     const fq v = sqrq(u), xx = sqrq(p.x);
@@ -404,129 +374,9 @@ __global__ __launch_bounds__(MSM_NB) void k_msm_reduce_chunks(uint8_t *ws, size_
     if (live && c == 0) fb_partial_store(((fb_partial *)(ws + b * per_blob + gsum_off))[g], S);
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Wave-cooperative XYZZ arithmetic for the serial tails.  A chain of dependent group operations on ONE point (the Horner over the
-// window groups: 120 doublings) is bound by the latency of one F_p product after the other on one SIMD.  The products INSIDE a
-// doubling / addition are mostly independent, so the four wavefronts of a 256-thread workgroup (one per SIMD of the CU) each take
-// one product of a dependency level and exchange the results through LDS: a doubling is 3 levels deep instead of 9 products, an
-// addition 4 instead of 13.  Lane column c of every wave works on the same point c (64 points per workgroup); all four waves keep
-// a full replica of the running point, so control flow stays identical across them.
-// LDS: two alternating sets of four 13-limb slots per column, limb-major (conflict-free), one barrier per level.
-// ---------------------------------------------------------------------------------------------------------
-struct coop_lds { uint32_t x[2][4][13][64]; };
-struct coop_ctx {
-    coop_lds *L; uint32_t wave, col, set;
-    __device__ __forceinline__ void put(const fq &v) {
-#pragma unroll
-        for (int i = 0; i < 13; i++) L->x[set][wave][i][col] = v.l[i];
-    }
-    __device__ __forceinline__ fq get(uint32_t slot) const {
-        fq v;
-#pragma unroll
-        for (int i = 0; i < 13; i++) v.l[i] = L->x[set][slot][i][col];
-        return v;
-    }
-    __device__ __forceinline__ void exchange() { __syncthreads(); }          // after put(), before get(): one barrier per level
-    __device__ __forceinline__ void next() { set ^= 1u; }                    // the following level writes the other set
-};
-// p <- 2 p (dbl-2008-s-1, a = 0) on lazy limbs, bounds (X, Y, ZZ, ZZZ) <= (11, 5, 2, 2) in and out:
-//   U = 2 Y : 10;  V = U^2, XX = X^2 : 2 (100, 121 <= 600);  M = 3 XX : 6;  W = U V, S = X V, ZZ' = V ZZ, MM = M^2 : 2
-//   X' = MM - 2 S (M = 5) : 7;  T1 = M (S - X') (S - X' with M = 8 : 10, 60), T2 = W Y : 2;  Y' = T1 - T2 (M = 3) : 5;  ZZZ' = W ZZZ : 2
-__device__ __forceinline__ void coop_xyzz_dbl(g1xq &p, coop_ctx &c) {
-    const fq u = addq(p.y, p.y);
-    fq mine;
-    if (c.wave == 0) mine = sqrq(u); else if (c.wave == 1) mine = sqrq(p.x); else mine = u;
-    c.put(mine); c.exchange();
-    const fq v = c.get(0), xx = c.get(1);
-    c.next();
-    const fq m = addq(addq(xx, xx), xx);
-    if (c.wave == 0) mine = mulq(u, v); else if (c.wave == 1) mine = mulq(p.x, v); else if (c.wave == 2) mine = mulq(v, p.zz); else mine = sqrq(m);
-    c.put(mine); c.exchange();
-    const fq w = c.get(0), s_ = c.get(1), zz3 = c.get(2), mm = c.get(3);
-    c.next();
-    const fq x3 = subq<5>(mm, addq(s_, s_));
-    if (c.wave == 0) mine = mulq(m, subq<8>(s_, x3)); else if (c.wave == 1) mine = mulq(w, p.y); else mine = mulq(w, p.zzz);
-    c.put(mine); c.exchange();
-    const fq t1 = c.get(0), t2 = c.get(1), zzz3 = c.get(2);
-    c.next();
-    p.x = x3; p.y = subq<3>(t1, t2); p.zz = zz3; p.zzz = zzz3;
-}
-// a <- a + b (add-2008-s), bounds as in g1xq_add_fast.  Returns false when P == 0 (equal / opposite operands): `a` is then
-// untouched and the caller takes the generic path.  All four waves compute the same verdict.
-__device__ __forceinline__ bool coop_xyzz_add(g1xq &a, const g1xq &b, coop_ctx &c) {
-    fq mine;
-    if (c.wave == 0) mine = mulq(a.x, b.zz); else if (c.wave == 1) mine = mulq(b.x, a.zz); else if (c.wave == 2) mine = mulq(a.y, b.zzz); else mine = mulq(b.y, a.zzz);
-    c.put(mine); c.exchange();
-    const fq u1 = c.get(0), u2 = c.get(1), s1 = c.get(2), s2 = c.get(3);
-    c.next();
-    const fq pp_ = subq<3>(u2, u1), r = subq<3>(s2, s1);
-    if (c.wave == 0) mine = sqrq(pp_); else if (c.wave == 1) mine = sqrq(r); else if (c.wave == 2) mine = mulq(a.zz, b.zz); else mine = mulq(a.zzz, b.zzz);
-    c.put(mine); c.exchange();
-    const fq pp = c.get(0), rr = c.get(1), zz12 = c.get(2), zzz12 = c.get(3);
-    c.next();
-    const bool ok = !is_zero_mod_p_q(pp);
-    if (c.wave == 0) mine = mulq(pp_, pp); else if (c.wave == 1) mine = mulq(u1, pp); else mine = mulq(zz12, pp);
-    c.put(mine); c.exchange();
-    const fq ppp = c.get(0), q_ = c.get(1), zz3 = c.get(2);
-    c.next();
-    const fq x3 = subq<3>(subq<3>(subq<3>(rr, ppp), q_), q_);
-    if (c.wave == 0) mine = mulq(r, subq<12>(q_, x3)); else if (c.wave == 1) mine = mulq(s1, ppp); else mine = mulq(zzz12, ppp);
-    c.put(mine); c.exchange();
-    const fq t1 = c.get(0), t2 = c.get(1), zzz3 = c.get(2);
-    c.next();
-    if (ok) { a.x = x3; a.y = subq<3>(t1, t2); a.zz = zz3; a.zzz = zzz3; }
-    return ok;
-}
-
-// acc += w for the replicated accumulators of a cooperating workgroup; called by all 256 threads (barriers inside).  Columns with
-// nothing to add (winf) still run the addition, on a private copy of whatever `w` holds, and drop the result.
-__device__ __forceinline__ void coop_acc_add(g1x_acc &acc, const g1xq &w, bool winf, coop_ctx &c) {
-    g1xq sum = acc.v, addend = w;                          // private copies: the operands must not move while the levels exchange
-    const bool ok = coop_xyzz_add(sum, addend, c);
-    if (winf) return;
-    if (acc.inf) { acc.v = addend; acc.inf = false; }
-    else if (ok) acc.v = sum;
-    else g1x_acc_merge(acc, addend, false);                // equal / opposite operands: generic complete formulas, identical on the four waves
-}
-
 // Horner over the window groups (8 doublings per group), then normalise and convert.  The doublings are the critical path of a
-// lone MSM (120 for 16 groups, 56 for 8): workgroup = 4 cooperating waves, lane column = blob (64 blobs per workgroup).
-#ifdef KZG_COMBINE_WAVE_COOP                                 // round 2's form: four WAVEFRONTS per blob column, exchange through LDS (A/B builds)
-__global__ __launch_bounds__(256) void k_msm_combine(uint8_t *ws, size_t per_blob, size_t gsum_off, uint32_t ngroups, uint64_t batch, g1j *out, int to_kilic) {
-    __shared__ coop_lds lds;
-    coop_ctx c; c.L = &lds; c.wave = threadIdx.x >> 6; c.col = threadIdx.x & 63u; c.set = 0;
-    const uint64_t b = blockIdx.x * 64ull + c.col;
-    const bool live = b < batch;
-    const fb_partial *gsum = (const fb_partial *)(ws + (live ? b : 0) * per_blob + gsum_off);
-    g1x_acc acc; acc.init();
-    acc.v = g1xq_from_affine(g1a_inf());                   // defined limbs while the accumulator is still empty (results are discarded)
-#pragma nounroll
-    for (uint32_t g = ngroups; g-- > 0;) {
-#pragma nounroll
-        for (uint32_t j = 0; j < 8; j++) {                 // barriers inside: every thread runs the doubling, empty accumulators ignore it
-            g1xq d = acc.v;
-            coop_xyzz_dbl(d, c);
-            if (!acc.inf) acc.v = d;
-        }
-        const bool winf = !live || gsum[g].inf != 0;
-        g1xq w;
-        if (winf) w = acc.v; else fb_partial_load(gsum[g], w);
-        coop_acc_add(acc, w, winf, c);
-    }
-    if (live && c.wave == 0) {
-        g1j r;
-        if (acc.inf) r = g1_inf();
-        else {   // x = X / ZZ, y = Y / ZZZ with one inversion
-            g1x px = g1xq_pack(acc.v);
-            fp i = inv<FpP>(mul(px.zz, px.zzz));
-            r.x = mul(px.x, mul(i, px.zzz)); r.y = mul(px.y, mul(i, px.zz)); r.z = one<FpP>();
-        }
-        out[b] = to_kilic ? g1_to_kilic(r) : r;
-    }
-}
-#else
-// Quad form (g1_quad.hpp): the four LANES of a quad hold the replicas and exchange the products of a level by DPP broadcasts -- no LDS, no barrier
-// (a level 1.3 us instead of 1.84).  64 blobs per 256-lane workgroup, as before.
+// lone MSM (120 for 16 groups, 56 for 8).  Quad form (g1_quad.hpp): the four LANES of a quad hold the replicas and exchange the products of a
+// level by DPP broadcasts -- no LDS, no barrier (a level 1.3 us instead of 1.84 with four wavefronts exchanging through LDS).  64 blobs per 256-lane workgroup.
 __global__ __launch_bounds__(256) void k_msm_combine(uint8_t *ws, size_t per_blob, size_t gsum_off, uint32_t ngroups, uint64_t batch, g1j *out, int to_kilic) {
     const uint32_t role = threadIdx.x & 3u;
     const uint64_t b = blockIdx.x * 64ull + (threadIdx.x >> 2);
@@ -560,7 +410,6 @@ __global__ __launch_bounds__(256) void k_msm_combine(uint8_t *ws, size_t per_blo
         }
     }
 }
-#endif
 
 void launch_msm(hipStream_t s, const msm_plan &p, const g1a *table, const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, void *workspace, g1j *out,
                 bool to_kilic) {
@@ -675,18 +524,15 @@ __global__ __launch_bounds__(FB_BLOCK, 2) void k_fb_build_pass2(uint64_t lanes, 
 // ---------------------------------------------------------------------------------------------------------
 // QUAD-cooperative reduction trees (round 6).  The trees at the end of the walk and in the finish are chains of dependent XYZZ additions: pure latency, and for a lone
 // commitment they ARE the call (19 additions on the critical path).  Rounds 2-5 spread the products of an addition over the four WAVEFRONTS of the workgroup
-// (coop_xyzz_add: one product per wave and dependency level, results exchanged through LDS, one workgroup barrier per level: 2.2 us per level, 8.8 us per addition).
+// (one product per wave and dependency level, results exchanged through LDS, one workgroup barrier per level: 2.2 us per level, 8.8 us per addition).
 // The four LANES of a quad do the same with DPP broadcasts -- no LDS, no barrier (g1_quad.hpp, the form k_msm_combine has used since round 3): ~1.5 us per level.
 // Column c of the 64 columns of a workgroup is quad c (lanes 4 c .. 4 c + 3, which hold replicas); tree levels fetch column c + off from lane + 4 off of the same
 // wavefront (DPP / ds_bpermute) or, for the two levels that cross wavefronts, through 32 + 16 LDS slots with one barrier each.
+// The tree sites inline the addition: one out-of-line copy for all of them measured a lone commitment 0.225 -> 0.265 ms, the 4096-blob walk unchanged (the call's
+// traffic through scratch costs more than warm instructions save).
 // ---------------------------------------------------------------------------------------------------------
-// (hook for an A/B: the tree sites call the addition through this name)
-#ifdef KZG_QUAD_ADD_NOINLINE                                  // A/B builds: one out-of-line copy of the addition for all tree sites (measured: a lone commitment 0.225 -> 0.265 ms,
-                                                             // the 4096-blob walk unchanged: the call's traffic through scratch costs more than warm instructions save)
-__device__ __noinline__ void quad_acc_add_nl(g1x_acc &acc, const g1xq &w, bool winf, uint32_t role) { quad_acc_add(acc, w, winf, role); }
-#else
-__device__ __forceinline__ void quad_acc_add_nl(g1x_acc &acc, const g1xq &w, bool winf, uint32_t role) { quad_acc_add(acc, w, winf, role); }
-#endif
+// the addition of the tree sites (calling quad_acc_add there directly gives the walk and finish kernels the same instructions in another schedule)
+__device__ __forceinline__ void quad_tree_add(g1x_acc &acc, const g1xq &w, bool winf, uint32_t role) { quad_acc_add(acc, w, winf, role); }
 template <int R> __device__ __forceinline__ void quad_point_bcast(g1xq &o, uint32_t &oinf, const g1xq &v, uint32_t vinf) {
     o.x = quad_bcast<R>(v.x); o.y = quad_bcast<R>(v.y); o.zz = quad_bcast<R>(v.zz); o.zzz = quad_bcast<R>(v.zzz);
     oinf = (uint32_t)__builtin_amdgcn_update_dpp((int)vinf, (int)vinf, R * 0x55, 0xf, 0xf, false);
@@ -704,7 +550,7 @@ __device__ __forceinline__ void quad_tree_reduce(g1x_acc &col, fb_partial *buf, 
             const bool have = quad + off < live;
             const fb_partial &src = buf[have ? quad + off : off];
             g1xq w; fb_partial_load(src, w);
-            quad_acc_add_nl(col, w, !have || src.inf != 0, role);
+            quad_tree_add(col, w, !have || src.inf != 0, role);
         }
     }
     if (tid < 64) {                                       // the rest is inside the first wavefront: column c + off is lane + 4 off
@@ -713,65 +559,26 @@ __device__ __forceinline__ void quad_tree_reduce(g1x_acc &col, fb_partial *buf, 
             const bool have = quad < off && quad + off < live;
             g1xq w; uint32_t wi;
             point_down_any(w, wi, col.v, col.inf ? 1u : 0u, 4 * off);
-            quad_acc_add_nl(col, w, !have || wi != 0, role);
+            quad_tree_add(col, w, !have || wi != 0, role);
         }
     }
 }
 // Block-wide sum of the 256 lane accumulators of a table-walk workgroup into lane 0's: the four accumulators of a quad first (three additions), then the tree
-// over the 64 quads: 9 additions like the wave-cooperative form below, each ~6 us instead of 8.8.
+// over the 64 quads: 9 additions, each ~6 us instead of the 8.8 of the four-wavefront form of rounds 2-5.
 __device__ __forceinline__ void fb_block_reduce_quad(g1x_acc &acc, fb_partial *buf, uint32_t tid) {
     const uint32_t role = tid & 3u;
     if (acc.inf) acc.v = g1xq_from_affine(g1a_inf());      // defined limbs in empty accumulators (their additions are computed and dropped)
     const uint32_t ainf = acc.inf ? 1u : 0u;
     g1x_acc col;
     { uint32_t vi; quad_point_bcast<0>(col.v, vi, acc.v, ainf); col.inf = vi != 0; }
-    { g1xq v; uint32_t vi; quad_point_bcast<1>(v, vi, acc.v, ainf); quad_acc_add_nl(col, v, vi != 0, role); }
-    { g1xq v; uint32_t vi; quad_point_bcast<2>(v, vi, acc.v, ainf); quad_acc_add_nl(col, v, vi != 0, role); }
-    { g1xq v; uint32_t vi; quad_point_bcast<3>(v, vi, acc.v, ainf); quad_acc_add_nl(col, v, vi != 0, role); }
+    { g1xq v; uint32_t vi; quad_point_bcast<1>(v, vi, acc.v, ainf); quad_tree_add(col, v, vi != 0, role); }
+    { g1xq v; uint32_t vi; quad_point_bcast<2>(v, vi, acc.v, ainf); quad_tree_add(col, v, vi != 0, role); }
+    { g1xq v; uint32_t vi; quad_point_bcast<3>(v, vi, acc.v, ainf); quad_tree_add(col, v, vi != 0, role); }
     quad_tree_reduce(col, buf, tid, 64);
     acc = col;                                             // quad 0 (lanes 0..3) holds the block's sum
 }
 
-// Block-wide sum of the 256 lane accumulators of a table-walk workgroup into lane 0's, WAVE-COOPERATIVELY: while the tree runs, three of
-// the four wavefronts would idle, so each takes one product of a dependency level of the XYZZ addition instead (coop_xyzz_add: 4 levels
-// deep instead of 13 products).  Lane column c of every wave keeps a replica of column c's running sum: the waves publish their 64
-// accumulators one after the other (3 cooperative additions), then a 6-level tree over the columns: 9 additions of depth 4 instead of
-// 7 of depth 13 (and 8 with 256 lanes).  The tree is what a small batch pays in full: a walk over 64 polynomials 0.86 -> 0.8x ms.
-// buf: 64 slots.
-#define FB_ACC_BLOCK 256
-__device__ __forceinline__ void fb_block_reduce_coop(g1x_acc &acc, fb_partial *buf, coop_lds *lds, uint32_t tid) {
-    coop_ctx c; c.L = lds; c.wave = tid >> 6; c.col = tid & 63u; c.set = 0;
-    g1x_acc col; col.init();
-#pragma nounroll
-    for (uint32_t w = 0; w < FB_ACC_BLOCK / 64; w++) {
-        if (c.wave == w) fb_partial_store(buf[c.col], acc);
-        __syncthreads();
-        g1xq v; fb_partial_load(buf[c.col], v);
-        const bool vinf = buf[c.col].inf != 0;
-        __syncthreads();                                   // everyone has read before the next wave publishes
-        if (w == 0) { col.v = v; col.inf = vinf; }
-        else coop_acc_add(col, v, vinf, c);
-    }
-#pragma nounroll
-    for (uint32_t off = 32; off >= 1; off >>= 1) {
-        const bool have = c.col < off;
-#ifdef KZG_NO_WAVE_SHUFFLE
-        if (c.wave == 0) fb_partial_store(buf[c.col], col);   // the replicas are identical: one wave publishes the columns
-        __syncthreads();
-        const uint32_t src = have ? c.col + off : c.col;
-        g1xq w; fb_partial_load(buf[src], w);
-        const bool winf = !have || buf[src].inf != 0;
-        __syncthreads();
-#else
-        // every wave holds all 64 columns (identical replicas): column c + off comes from lane c + off of the SAME wave
-        g1xq w; uint32_t wi;
-        point_down_any(w, wi, col.v, col.inf ? 1u : 0u, off);
-        const bool winf = !have || wi != 0;
-#endif
-        coop_acc_add(col, w, winf, c);
-    }
-    acc = col;                                             // column 0 (of every wave) holds the block's sum
-}
+#define FB_ACC_BLOCK 256        // threads per table-walk workgroup
 __device__ __forceinline__ uint32_t scalar_bits(const fr &k, uint32_t off, uint32_t c) {
     uint32_t idx = off >> 5, sh = off & 31;
     if (idx >= 8) return 0;
@@ -788,9 +595,6 @@ __device__ __forceinline__ uint32_t scalar_bits(const fr &k, uint32_t off, uint3
 template <bool SPLIT> __global__ __launch_bounds__(FB_ACC_BLOCK, FB_ACC_WAVES) void k_fb_accumulate(const g1a *table, uint64_t table_n, uint32_t c, uint32_t nwin, uint32_t D, const fr *scalars,
                                                             uint64_t sc_stride, uint64_t n, uint32_t blocks_per_blob, uint32_t wsplit, fb_partial *partials) {
     __shared__ fb_partial buf[64];
-#ifdef KZG_REDUCE_WAVE_COOP
-    __shared__ coop_lds lds;
-#endif
     const uint32_t tid = threadIdx.x;
     const uint64_t blob = blockIdx.x / blocks_per_blob; const uint32_t blk = blockIdx.x % blocks_per_blob;
     const uint64_t L = (uint64_t)blocks_per_blob * FB_ACC_BLOCK;
@@ -812,17 +616,6 @@ template <bool SPLIT> __global__ __launch_bounds__(FB_ACC_BLOCK, FB_ACC_WAVES) v
         }
         raw = scalar_bits(k, w0 * c, c) + carry;
         if (raw > D) { carry = 1; mag = (1u << c) - raw; ng = 1; } else { carry = 0; mag = raw; ng = 0; }
-#ifdef KZG_WALK_NO_PREFETCH                                   // A/B builds: gather at the point of use (no register-held next entry)
-#pragma nounroll
-        for (uint32_t w = w0; w < w1; w++) {
-            const uint32_t cmag = mag, cng = ng;
-            g1a q = table[((uint64_t)w * table_n + i) * D + (cmag ? cmag - 1 : 0)];
-            if (w + 1 < w1) {
-                raw = scalar_bits(k, (w + 1) * c, c) + carry;
-                if (raw > D) { carry = 1; mag = (1u << c) - raw; ng = 1; } else { carry = 0; mag = raw; ng = 0; }
-            }
-            if (cmag) {
-#else
         g1a qn = table[((uint64_t)w0 * table_n + i) * D + (mag ? mag - 1 : 0)];
 #pragma nounroll
         for (uint32_t w = w0; w < w1; w++) {
@@ -834,17 +627,12 @@ template <bool SPLIT> __global__ __launch_bounds__(FB_ACC_BLOCK, FB_ACC_WAVES) v
                 qn = table[((uint64_t)(w + 1) * table_n + i) * D + (mag ? mag - 1 : 0)];
             }
             if (cmag) {
-#endif
                 if (cng) q.y = neg<FpP>(q.y);
                 acc.add(q);
             }
         }
     }
-#ifdef KZG_REDUCE_WAVE_COOP                                   // A/B builds: the four-wavefront form of rounds 2-5
-    fb_block_reduce_coop(acc, buf, &lds, tid);
-#else
     fb_block_reduce_quad(acc, buf, tid);
-#endif
     if (tid == 0) fb_partial_store(partials[blockIdx.x], acc);
 }
 // The same walk over a table HALF as large (round 5): every scalar is split on the device, k = s1 |k1| + s2 |k2| lambda with both magnitudes below
@@ -863,9 +651,6 @@ __device__ __forceinline__ uint32_t mag_bits(const uint32_t (&m)[4], uint32_t of
 template <bool SPLIT> __global__ __launch_bounds__(FB_ACC_BLOCK, FB_ACC_WAVES) void k_fb_accumulate_glv(const g1a *table, uint64_t table_n, uint32_t c, uint32_t nwin, uint32_t D, const fr *scalars,
                                                             uint64_t sc_stride, uint64_t n, uint32_t blocks_per_blob, uint32_t wsplit, fb_partial *partials) {
     __shared__ fb_partial buf[64];
-#ifdef KZG_REDUCE_WAVE_COOP
-    __shared__ coop_lds lds;
-#endif
     const uint32_t tid = threadIdx.x;
     const uint64_t blob = blockIdx.x / blocks_per_blob; const uint32_t blk = blockIdx.x % blocks_per_blob;
     const uint64_t L = (uint64_t)blocks_per_blob * FB_ACC_BLOCK;
@@ -933,51 +718,17 @@ template <bool SPLIT> __global__ __launch_bounds__(FB_ACC_BLOCK, FB_ACC_WAVES) v
         }
     }
     if (in_phi && !acc.inf) acc.v.x = mulq(acc.v.x, unpackq(glv_beta()));   // a lane that only held phi halves
-#ifdef KZG_REDUCE_WAVE_COOP                                   // A/B builds: the four-wavefront form of rounds 2-5
-    fb_block_reduce_coop(acc, buf, &lds, tid);
-#else
     fb_block_reduce_quad(acc, buf, tid);
-#endif
     if (tid == 0) fb_partial_store(partials[blockIdx.x], acc);
 }
-// one workgroup of four cooperating wavefronts per blob (lane column j = partial sum j): the blob's partial sums are added by a
-// tree of wave-cooperative XYZZ additions (4 products deep instead of 13; a lone commitment has 32 partials: 5 levels), then
-// column 0 normalises (one inversion: 1 / (ZZ ZZZ)) and converts.  This kernel is pure latency: ~100 us instead of ~230.
+// one 256-lane workgroup per blob (quad column c = partial sums c, c + 64, ...): the blob's partial sums are added by a tree of
+// quad-cooperative XYZZ additions (4 products deep instead of 13; a lone commitment has 32 partials: 5 levels), then quad 0
+// normalises (one inversion: 1 / (ZZ ZZZ)) and converts.  This kernel is pure latency: ~100 us instead of ~230.
 __global__ __launch_bounds__(256) void k_fb_finish(const fb_partial *partials, uint32_t blocks_per_blob, uint64_t batch, g1j *out, int to_kilic) {
     __shared__ fb_partial buf[64];
     const uint64_t b = blockIdx.x;
-#ifdef KZG_REDUCE_WAVE_COOP                                   // A/B builds: the four-wavefront form of rounds 2-5 (lane column = partial sum, replicas across the wavefronts)
-    __shared__ coop_lds lds;
-    coop_ctx c; c.L = &lds; c.wave = threadIdx.x >> 6; c.col = threadIdx.x & 63u; c.set = 0;
-    const uint32_t col = c.col;
-    g1x_acc acc; acc.init();
-    acc.v = g1xq_from_affine(g1a_inf());                   // defined limbs while empty
-    const uint32_t rounds = (blocks_per_blob + 63) / 64;
-#pragma nounroll
-    for (uint32_t r = 0; r < rounds; r++) {
-        const uint32_t j = r * 64 + col;
-        const bool have = j < blocks_per_blob;
-        const fb_partial &pj = partials[b * blocks_per_blob + (have ? j : 0)];
-        g1xq w; fb_partial_load(pj, w);
-        coop_acc_add(acc, w, !have || pj.inf != 0, c);
-    }
-    const uint32_t live = blocks_per_blob < 64 ? blocks_per_blob : 64;
-    uint32_t off = 1;
-    while (off < live) off *= 2;                          // smallest power of two >= live
-#pragma nounroll
-    for (off >>= 1; off >= 1; off >>= 1) {
-        const bool have = col < off && col + off < live;
-        g1xq w; uint32_t wi;                               // column col + off lives in lane col + off of the same wave (replicas)
-        point_down_any(w, wi, acc.v, acc.inf ? 1u : 0u, off);
-        coop_acc_add(acc, w, !have || wi != 0, c);
-    }
-    const bool first_wave = c.wave == 0;
-#else
     // quad column c = lanes 4 c .. 4 c + 3 (replicas) takes the partial sums c, c + 64, ...; then the quad tree; quad 0 ends with the blob's sum (k_msm.hip, above)
     const uint32_t tid = threadIdx.x, role = tid & 3u, quad = tid >> 2, col = tid & 63u;
-#ifdef KZG_FINISH_TIMING
-    const uint64_t tf0 = wall_clock64();
-#endif
     g1x_acc acc; acc.init();
     acc.v = g1xq_from_affine(g1a_inf());                   // defined limbs while empty
     const uint32_t rounds = (blocks_per_blob + 63) / 64;
@@ -993,31 +744,16 @@ __global__ __launch_bounds__(256) void k_fb_finish(const fb_partial *partials, u
             const fb_partial &pj = partials[b * blocks_per_blob + (have ? j : 0)];
             fb_partial_load(pj, wn); wn_inf = !have || pj.inf != 0;
         }
-        quad_acc_add_nl(acc, w, winf, role);
+        quad_tree_add(acc, w, winf, role);
     }
-#ifdef KZG_FINISH_TIMING
-    __syncthreads(); const uint64_t tf1 = wall_clock64();
-#endif
     quad_tree_reduce(acc, buf, tid, blocks_per_blob < 64 ? blocks_per_blob : 64);
-#ifdef KZG_FINISH_TIMING
-    __syncthreads(); const uint64_t tf2 = wall_clock64();
-#endif
     const bool first_wave = tid < 64;
-#endif
     if (first_wave) {                                       // wave-uniform: the whole first wavefront takes part in the inversion, its lane 0 owns the result
         const bool own = col == 0;
         const g1x px = g1xq_pack(acc.v);                    // (defined limbs in every column: empty accumulators hold the affine image of infinity)
         // x = X / ZZ, y = Y / ZZZ with ONE inversion: i = 1 / (ZZ ZZZ), 1 / ZZ = i ZZZ, 1 / ZZZ = i ZZ -- spread over the wavefront's lanes (coop_inv.hpp)
         const bool need = own && !acc.inf && !(to_kilic & 2);
-#ifdef KZG_FINISH_NOINV                                      // timing experiment only (wrong results): what the inversion costs
-        const fp i = mul(px.zz, px.zzz);
-#elif defined(KZG_NO_COOP_INV)
-        fp i = zero<FpP>();
-        if (need) i = inv<FpP>(mul(px.zz, px.zzz));
-#else
         const fp i = wave_inv_any(mul(px.zz, px.zzz), need);
-#endif
-#if !defined(KZG_REDUCE_WAVE_COOP) && !defined(KZG_NO_COOP_INV) && !defined(KZG_FINISH_NOINV)
         // the affine image: x = X i ZZZ on lane 0, y = Y i ZZ on lane 1 (quad 0 holds replicas of the sum; the inverse is the owner's: handed to lane 1 by a DPP move), each
         // followed by its own conversion to Kilic's image -- three dependent products per lane instead of six on one
         const uint32_t aff = __builtin_amdgcn_readfirstlane((uint32_t)(!acc.inf && !(to_kilic & 2)));
@@ -1037,19 +773,7 @@ __global__ __launch_bounds__(256) void k_fb_finish(const fb_partial *partials, u
             if (acc.inf) r = g1_inf(); else r = g1x_to_jac(px);  // infinity, or the projective output (kzg_hip_kzg_set_projective_outputs): (X ZZ, Y ZZZ, ZZ), no inversion
             out[b] = (to_kilic & 1) ? g1_to_kilic(r) : r;
         }
-#else
-        if (own) {
-            g1j r;
-            if (acc.inf) r = g1_inf();
-            else if (to_kilic & 2) r = g1x_to_jac(px);       // projective output (kzg_hip_kzg_set_projective_outputs): (X ZZ, Y ZZZ, ZZ), no inversion
-            else { r.x = mul(px.x, mul(i, px.zzz)); r.y = mul(px.y, mul(i, px.zz)); r.z = one<FpP>(); }
-            out[b] = (to_kilic & 1) ? g1_to_kilic(r) : r;
-        }
-#endif
     }
-#if defined(KZG_FINISH_TIMING) && !defined(KZG_REDUCE_WAVE_COOP)
-    if (threadIdx.x == 0 && b == 0) printf("finish phases (us): %u rounds of load + add %.1f | tree %.1f | inversion + output %.1f\n", (blocks_per_blob + 63) / 64, (tf1 - tf0) * 0.01, (tf2 - tf1) * 0.01, (wall_clock64() - tf2) * 0.01);
-#endif
 }
 
 // The same for LARGE batches (at most 4 partial sums per blob: 128 blobs and more): one LANE per blob adds its few partials and

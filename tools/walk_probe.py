@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time of the commitment step alone (kzg_hip_commit_to_poly_batch_dev on device-resident blobs): ms per step, median of the timed steps.
-For A/B builds selected with KZG_HIP_LIB -- including timing-only variants whose results are wrong on purpose (bench.py would refuse them).
+For A/B builds selected with KZG_HIP_LIB: it times the step and does not check the commitments.
 usage: python tools/walk_probe.py [batch [table_gb [steps]]]"""
 import os, sys, time
 import numpy as np
