@@ -4,6 +4,7 @@
 // (kzg_single_proofs.go:57, kzg_multi_proofs.go:47) and eth.VerifyKZGProof (eth/eth.go:114, eth/helpers.go:55).
 #include "internal.hpp"
 #include "pairing.hpp"
+#include "verify_inputs.hpp"
 
 namespace kzg {
 
@@ -11,22 +12,6 @@ namespace kzg {
 // check kernel is register-bound whatever the block size; 64 lanes keep the tail of a small batch to one wavefront.
 #define PAIRING_BLOCK 64
 static inline dim3 pairing_grid(uint64_t n) { return dim3((uint32_t)((n + PAIRING_BLOCK - 1) / PAIRING_BLOCK)); }
-
-__device__ __forceinline__ g1j g1_generator_internal() {   // bls.GenG1 (standard literals into the device-internal domain)
-    const uint32_t gx[12] = {0xdb22c6bbu, 0xfb3af00au, 0xf97a1aefu, 0x6c55e83fu, 0x171bac58u, 0xa14e3a3fu,
-                             0x9774b905u, 0xc3688c4fu, 0x4fa9ac0fu, 0x2695638cu, 0x3197d794u, 0x17f1d3a7u};
-    const uint32_t gy[12] = {0x46c5e7e1u, 0x0caa2329u, 0xa2888ae4u, 0xd03cc744u, 0x2c04b3edu, 0x00db18cbu,
-                             0xd5d00af6u, 0xfcf5e095u, 0x741d8ae4u, 0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u};
-    g1j g; g.x = to_mont<FpP>(fp_const(gx)); g.y = to_mont<FpP>(fp_const(gy)); g.z = one<FpP>();
-    return g;
-}
-// k P for a STANDARD-form scalar: the device GLV split and the regular odd-digit schedule of the G1 kernels (g1.hpp)
-__device__ __forceinline__ g1j g1_mul_std(const g1j &p, const fr &k_std) {
-    if (is_inf(p)) return g1_inf();
-    g1aq tbl[8]; fq dz[7]; g1jq q; g1j packed;
-    const int st = g1_mul_glv_regular_aq<false>(g1jq_unpack(p), glv_split_signed(k_std), tbl, dz, q, packed);
-    return st == 1 ? g1jq_pack(q) : st == 2 ? packed : g1_inf();
-}
 
 __global__ __launch_bounds__(PAIRING_BLOCK) void k_g2_from_compressed(const uint8_t *in96, g2j *out, uint64_t n, uint32_t *bad) {
     const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -64,17 +49,13 @@ void launch_pairs_g1_from_kilic(hipStream_t s, const g1j *a1, const g1j *b1, uin
     hipLaunchKernelGGL(k_pairs_g1_from_kilic, pairing_grid(n), dim3(PAIRING_BLOCK), 0, s, a1, b1, n, p0, p1);
 }
 
-// G1 inputs of a KZG check e(C - E + [b] pi, G2) e(-pi, [s^k] G2) == 1 (c-kzg's arrangement: no G2 scalar multiplication per check):
-//   single proof (ys != null): E = [y] G1, b = z;   multi proof (ys == null): E = es[i] = [I(s)]_1, b = x^n.
-// Kilic images and Kilic-Montgomery scalars in.
+// G1 inputs of a KZG check (kzg_check_inputs_lane, verify_inputs.hpp): single proofs with ys != null (E = [y] G1, b = z), multi proofs with
+// ys == null (E = es[i] = [I(s)]_1, b = x^n).  Kilic images and Kilic-Montgomery scalars in.
 __global__ __launch_bounds__(PAIRING_BLOCK) void k_kzg_check_inputs(const g1j *c, const g1j *pi, const fr *ys, const g1j *es, const fr *bs, uint64_t n,
                                                                     g1j *p0, g1j *p1) {
     const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const g1j pr = g1_from_kilic(pi[t]);
-    const g1j e = ys ? g1_mul_std(g1_generator_internal(), from_mont<FrP>(ys[t])) : g1_from_kilic(es[t]);
-    p0[t] = g1_add(g1_sub(g1_from_kilic(c[t]), e), g1_mul_std(pr, from_mont<FrP>(bs[t])));
-    p1[t] = g1_neg(pr);
+    kzg_check_inputs_lane(c[t], pi[t], ys, es, t, bs[t], p0[t], p1[t]);
 }
 void launch_kzg_check_inputs(hipStream_t s, const g1j *c, const g1j *pi, const fr *ys, const g1j *es, const fr *bs, uint64_t n, g1j *p0, g1j *p1) {
     if (!n) return;
@@ -96,25 +77,13 @@ void launch_fr_rows_scale_by_inv_powers(hipStream_t s, fr *c, uint64_t np, const
     hipLaunchKernelGGL(k_fr_rows_scale_by_inv_powers, pairing_grid(count), dim3(PAIRING_BLOCK), 0, s, c, np, xs, count, xpow_n);
 }
 
-// eth.VerifyKZGProof's parsing (eth/eth.go:114-135) and the G1 inputs of its check: status 0 = inputs valid, 2 = z or y not below r,
-// 3 = commitment or proof not a valid compressed G1 point (subgroup included).  Invalid rows get points at infinity.
-__device__ bool fr_from_le32_checked(fr &o, const uint8_t *b) {
-    for (int i = 0; i < 8; i++) o.l[i] = (uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 | (uint32_t)b[4 * i + 3] << 24;
-    for (int i = 7; i >= 0; i--) { const uint32_t m = FrP::mod(i); if (o.l[i] < m) return true; if (o.l[i] > m) return false; }
-    return false;
-}
+// eth.VerifyKZGProof's parsing and the G1 inputs of its check (eth_check_inputs_lane, verify_inputs.hpp): status 0 = inputs valid,
+// 2 = z or y not below r, 3 = commitment or proof not a valid compressed G1 point.  Invalid rows get points at infinity.
 __global__ __launch_bounds__(PAIRING_BLOCK) void k_eth_check_inputs(const uint8_t *c48, const uint8_t *zs, const uint8_t *ys, const uint8_t *pi48, uint64_t n,
                                                                     g1j *p0, g1j *p1, uint8_t *status) {
     const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (t >= n) return;
-    p0[t] = g1_inf(); p1[t] = g1_inf();
-    fr z, y;
-    if (!fr_from_le32_checked(z, zs + 32 * t) || !fr_from_le32_checked(y, ys + 32 * t)) { status[t] = 2; return; }
-    g1j c, pr;
-    if (!g1_decompress(c, c48 + 48 * t) || !g1_decompress(pr, pi48 + 48 * t)) { status[t] = 3; return; }
-    status[t] = 0;
-    p0[t] = g1_add(g1_sub(c, g1_mul_std(g1_generator_internal(), y)), g1_mul_std(pr, z));
-    p1[t] = g1_neg(pr);
+    eth_check_inputs_lane(c48 + 48 * t, zs + 32 * t, ys + 32 * t, pi48 + 48 * t, p0[t], p1[t], status[t]);
 }
 void launch_eth_check_inputs(hipStream_t s, const uint8_t *c48, const uint8_t *zs, const uint8_t *ys, const uint8_t *pi48, uint64_t n, g1j *p0, g1j *p1,
                              uint8_t *status) {

@@ -246,6 +246,8 @@ int kzg_hip_eth_evaluate_polynomial_in_evaluation_form(kzg_hip_eth *eth, const v
 /* ---- verification (bls/bls_kilic.go:121-158, kzg_single_proofs.go:57, kzg_multi_proofs.go:47, eth/eth.go:114, eth/helpers.go:55) ----
  * BATCH forms only: one lane per check (multi-Miller loop over two pairs + final exponentiation on the device).  Results are one byte per check.
  * A check before its G2 setter is KZG_HIP_ERR_BAD_ARG; count == 0 is KZG_HIP_OK.
+ * The G1 images given to kzg_hip_pairings_verify_batch and kzg_hip_check_proof_{single,multi}_batch are not checked and must lie in G1: a row
+ * that holds any other curve point has an unspecified result (the call still returns KZG_HIP_OK and no other row is affected).
  * kzg_hip_g2_from_compressed: bls.FromCompressedG2 over n 96-byte ZCash encodings -> n G2 images; KZG_HIP_ERR_BAD_POINT if ANY is invalid
  * (flags, x >= p, not on the curve, not in the subgroup), like kzg_hip_g1_from_compressed. */
 int kzg_hip_g2_from_compressed(kzg_hip_fft *fs, const void *in96, uint64_t n, void *out_g2);

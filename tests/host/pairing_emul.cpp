@@ -1,6 +1,8 @@
-// Host build of tower.hpp / g2.hpp / pairing.hpp for tests/test_pairing_host.py.  Every F_p value crosses this boundary in STANDARD form
-// (12 little-endian u32 limbs, < p); F_p12 values as 12 such elements in the order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1.
+// Host build of tower.hpp / g2.hpp / pairing.hpp / verify_inputs.hpp for tests/test_pairing_host.py.  Every F_p value crosses this boundary in
+// STANDARD form (12 little-endian u32 limbs, < p); F_p12 values as 12 such elements in the order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1.
+// The hooks of the check-input lanes take the C ABI's own memory images (Kilic G1 / G2 / F_r, compressed bytes) instead.
 #include "pairing.hpp"
+#include "verify_inputs.hpp"
 
 using namespace kzg;
 
@@ -70,4 +72,67 @@ int pe_pairing_check2(const uint32_t *g1, const uint32_t *g2) {
     const g2_prepared *qs[2] = {&prep[0], &prep[1]};
     return pairing_product_is_one<2>(qs, p) ? 1 : 0;
 }
+
+// ---- the check-input lanes (verify_inputs.hpp) in front of the two-pair check, as capi_verify.hip chains them ----
+uint64_t pe_sizeof_prepared() { return sizeof(g2_prepared); }
+// what k_g2_prepare does with one Kilic image (any Jacobian Z): g2_from_kilic, g2_to_affine, g2_prepare.  kilic == null: bls.GenG2
+void pe_g2_prepare_kilic(const g2j *kilic, g2_prepared *out) {
+    const g2j p = g2_from_kilic(kilic ? *kilic : g2_to_kilic(g2_generator()));
+    g2_prepare(out, g2_to_affine(p), is_inf(p));
 }
+// the affine point behind a Kilic Jacobian image, through g2_from_kilic + g2_to_affine (x0, x1, y0, y1); returns 1 for infinity
+int pe_g2_kilic_to_affine(const g2j *kilic, uint32_t *out) {
+    const g2j p = g2_from_kilic(*kilic);
+    g2a a = g2_to_affine(p);
+    out_fp2(out, a.x); out_fp2(out + 24, a.y);
+    return is_inf(p) ? 1 : 0;
+}
+// k_kzg_check_inputs + k_pairing_check<true> over n rows: Kilic images c, pi (and es when ys == null), Kilic-Montgomery ys / bs
+void pe_kzg_check_batch(uint64_t n, const g1j *c, const g1j *pi, const fr *ys, const g1j *es, const fr *bs, const g2_prepared *gen, const g2_prepared *q1,
+                        uint8_t *ok) {
+    const g2_prepared *qs[2] = {gen, q1};
+    for (uint64_t t = 0; t < n; t++) {
+        g1j p[2];
+        kzg_check_inputs_lane(c[t], pi[t], ys, es, t, bs[t], p[0], p[1]);
+        ok[t] = pairing_product_is_one<2>(qs, p) ? 1 : 0;
+    }
+}
+// k_eth_check_inputs + k_pairing_check<true> + the status overlay of kzg_hip_eth_verify_kzg_proof_batch: 1 / 0, or the row's status 2 / 3
+void pe_eth_check_batch(uint64_t n, const uint8_t *c48, const uint8_t *zs, const uint8_t *ys, const uint8_t *pi48, const g2_prepared *gen,
+                        const g2_prepared *q1, uint8_t *result) {
+    const g2_prepared *qs[2] = {gen, q1};
+    for (uint64_t t = 0; t < n; t++) {
+        g1j p[2];
+        uint8_t st = 0;
+        eth_check_inputs_lane(c48 + 48 * t, zs + 32 * t, ys + 32 * t, pi48 + 48 * t, p[0], p[1], st);
+        const uint8_t ok = pairing_product_is_one<2>(qs, p) ? 1 : 0;
+        result[t] = st ? st : ok;
+    }
+}
+}
+
+#ifdef PE_MAIN
+// Stand-alone form for a sanitizer build: reads one single-proof batch (u64 n | n x c | n x pi | n x y | n x b | one Kilic G2 image of [s] G2)
+// from the file named on the command line, runs pe_kzg_check_batch, prints the mask as a line of 0 / 1.
+#include <stdio.h>
+#include <vector>
+int main(int argc, char **argv) {
+    if (argc != 2) return 2;
+    FILE *f = fopen(argv[1], "rb");
+    if (!f) return 2;
+    uint64_t n = 0;
+    if (fread(&n, sizeof n, 1, f) != 1 || n == 0 || n > 4096) return 2;
+    std::vector<g1j> c(n), pi(n); std::vector<fr> ys(n), bs(n); g2j q;
+    if (fread(c.data(), sizeof(g1j), n, f) != n || fread(pi.data(), sizeof(g1j), n, f) != n || fread(ys.data(), sizeof(fr), n, f) != n ||
+        fread(bs.data(), sizeof(fr), n, f) != n || fread(&q, sizeof q, 1, f) != 1) return 2;
+    fclose(f);
+    std::vector<g2_prepared> prep(2);
+    pe_g2_prepare_kilic(nullptr, &prep[0]);
+    pe_g2_prepare_kilic(&q, &prep[1]);
+    std::vector<uint8_t> ok(n);
+    pe_kzg_check_batch(n, c.data(), pi.data(), ys.data(), nullptr, bs.data(), &prep[0], &prep[1], ok.data());
+    for (uint64_t i = 0; i < n; i++) putchar(ok[i] ? '1' : '0');
+    putchar('\n');
+    return 0;
+}
+#endif

@@ -1,13 +1,19 @@
 """Verification on the device (k_pairing.hip, capi_verify.hip): pairing values against the Python reference, batched PairingsVerify, the
 reference's pairing-based proof tests restated (kzg_single_proofs_test.go, fk20_single_test.go, kzg_multi_proofs_test.go, fk20_multi_test.go),
-a 4096-proof batch with tampered rows, and eth.VerifyKZGProof end to end on the trusted setup's G2 points (tests/golden/trusted_setup_g2.json)."""
+a 4096-proof batch with tampered rows, and eth.VerifyKZGProof end to end on the trusted setup's G2 points (tests/golden/trusted_setup_g2.json).
+Then the adversarial side: the crafted rows of tests/verify_cases.py (exceptional cases of the group law that are valid and invalid), G2 images
+with Jacobian Z != 1, pairing values at batch size, the chunk loop of pairings_verify_batch, eth byte rows."""
 import json
 import os
+import random
+import time
 
 import numpy as np
 import pytest
 
 import pairing_ref as pr
+import verify_cases as vc
+import verify_images as vi
 from oracle import koracle as ko
 
 pytestmark = pytest.mark.gpu
@@ -323,3 +329,245 @@ def test_concurrent_checks_and_setters_on_one_handle(kz, g2_powers):
         t.join()
     assert not errors, errors
     ks.close(); fs.close()
+
+
+# ---------------- crafted rows (tests/verify_cases.py), Jacobian G2 images, chunk edges ----------------
+# Truth values come from scalars (the setup's secret is known here), points from the C oracle or the Python reference; nothing below asks the
+# library what the right answer is.  Each test prints how its wall time splits between building the expectation and the device calls.
+def report(name, t_ref, t_dev):
+    print("[timing] %s: reference %.2f s, device %.3f s" % (name, t_ref, t_dev))
+
+
+def tower_to_flat(val):
+    return pr.from_tower([(val[2 * k], val[2 * k + 1]) for k in range(6)])
+
+
+def test_pairing_values_at_batch_size(kz):
+    """200 pairs (three wavefronts and a tail of 8) with full-width scalars, random Jacobian Z on both sides (Z in F_p2 for G2), and infinity on
+    either or both sides at the wavefront edges: every VALUE equals e(G1, G2)^(a b), and four of them the reference pairing computed directly"""
+    rng = random.Random(31)
+    t0 = time.perf_counter()
+    n = 200
+    a0, da, b0, db = (vc.rand_fr(rng) for _ in range(4))
+    Ps, Qs = [pr.g1_mul(pr.G1_GEN, a0)], [pr.g2_mul(pr.G2_GEN, b0)]
+    step1, step2 = pr.g1_mul(pr.G1_GEN, da), pr.g2_mul(pr.G2_GEN, db)
+    for _ in range(n - 1):
+        Ps.append(pr.g1_add(Ps[-1], step1)); Qs.append(pr.g2_add(Qs[-1], step2))
+    inf1, inf2, both = {0, 64, 130, 197}, {63, 100, 199}, {31, 65, 128}
+    g1 = np.stack([ko.g1_zero(1)[0] if i in inf1 | both else vi.g1_rescale(vi.g1_affine_image(*Ps[i]), rng.randrange(1, pr.P)) for i in range(n)])
+    g2 = np.stack([vi.g2_kilic(None if i in inf2 | both else Qs[i], vi.rand_fp2(rng) if i % 5 else (1, 0)) for i in range(n)])
+    e0 = pr.pairing(pr.G1_GEN, pr.G2_GEN, DEVICE_EXP)
+    want = [pr.ONE12 if i in inf1 | inf2 | both else pr.f12pow(e0, (a0 + i * da) * (b0 + i * db) % pr.R) for i in range(n)]
+    direct = (1, 62, 66, 198)
+    for i in direct:
+        assert want[i] == pr.pairing(Ps[i], Qs[i], DEVICE_EXP), i           # the expectation does not rest on bilinearity alone
+    t1 = time.perf_counter()
+    fs = kz.FFTSettings(4)
+    got = fs.pairing_test(g1, g2)
+    t2 = time.perf_counter()
+    bad = [i for i in range(n) if tower_to_flat(got[i]) != want[i]]
+    assert not bad, bad
+    fs.close()
+    report("pairing values x200", t1 - t0 + time.perf_counter() - t2, t2 - t1)
+
+
+def row_bit(i, salt):
+    return (((i + salt) * 0x9E3779B1) >> 13) & 1
+
+
+def test_pairings_verify_batch_across_chunks(kz):
+    """n = 2 * 8192 + 5: the chunk loop runs three times, the last chunk short.  Row i pairs [k + 1] G1 with [m + 1] G2 against [m + 1] G1 with
+    [k + 1] G2 (k = i % 17, m = (i // 17) % 17; 17 is coprime to the chunk size, so a row read from the wrong chunk or the wrong half of the
+    staging buffers meets other points) and is spoiled or not by a hash bit of i; the rows at the chunk edges are set by hand"""
+    rng = random.Random(32)
+    t0 = time.perf_counter()
+    n = 2 * 8192 + 5
+    A = np.stack([g1_mul_int(a) for a in range(1, 18)])
+    Qref = [pr.g2_mul(pr.G2_GEN, a) for a in range(1, 18)]
+    Q = np.stack([np.stack([vi.g2_kilic(q), vi.g2_kilic(q, vi.rand_fp2(rng))]) for q in Qref])        # [k][0]: Z = 1, [k][1]: Z in F_p2
+    idx = np.arange(n)
+    k, m = idx % 17, (idx // 17) % 17
+    truth = np.array([row_bit(i, 0) for i in range(n)], dtype=bool)
+    for i, w in ((8190, False), (8191, True), (8192, False), (8193, True), (16382, True), (16383, False), (16384, True), (16388, False)):
+        truth[i] = w
+    jz_a = np.array([row_bit(i, 1) for i in range(n)])
+    jz_b = np.array([row_bit(i, 2) for i in range(n)])
+    a1, a2, b1 = A[k], Q[m, jz_a], A[m]
+    b2 = Q[np.where(truth, k, (k + 1) % 17), jz_b]
+    assert 0.4 < truth.mean() < 0.6 and 0.4 < jz_a.mean() < 0.6
+    t1 = time.perf_counter()
+    fs = kz.FFTSettings(4)
+    got = fs.pairings_verify_batch(a1, a2, b1, b2)
+    wrong = np.nonzero(got != truth)[0]
+    assert wrong.size == 0, wrong[:20]
+    for small in (1, 63, 64, 65):
+        lo = 8192 - small                                                     # a window of the same rows that starts elsewhere
+        assert np.array_equal(fs.pairings_verify_batch(a1[:small], a2[:small], b1[:small], b2[:small]), truth[:small]), small
+        assert np.array_equal(fs.pairings_verify_batch(a1[lo:8192], a2[lo:8192], b1[lo:8192], b2[lo:8192]), truth[lo:8192]), small
+    t2 = time.perf_counter()
+    fs.close()
+    report("pairings_verify_batch x16389", t1 - t0, t2 - t1)
+
+
+def padded_single_rows(s, total):
+    rows = vc.single_rows(s, random.Random(1))
+    seed = 100
+    while len(rows) < total:
+        extra = [r for r in vc.single_rows(s, random.Random(seed)) if r[0].startswith("ordinary/")]
+        rows += [("pad%d/" % seed + r[0],) + r[1:] for r in extra][:total - len(rows)]
+        seed += 1
+    return rows
+
+
+@pytest.fixture(scope="module")
+def ks16_jacobian(kz, g2_powers):   # the same settings, SecretG2 as un-normalised Jacobian images (what setup.go:20 leaves)
+    rng = random.Random(33)
+    fs = kz.FFTSettings(5)
+    ks = kz.KZGSettings(fs, ko.generate_testing_setup_g1(S_TEST, 33))
+    ks.set_secret_g2(np.stack([vi.g2_kilic(Q, vi.rand_fp2(rng)) for Q in g2_powers]))
+    yield ks
+    ks.close()
+    fs.close()
+
+
+def test_crafted_single_rows_on_the_device(kz, ks16, ks16_jacobian):
+    """every single row of verify_cases in one shuffled batch of 2 * 64 + 37 (exceptional and ordinary rows share wavefronts), then every
+    exceptional row as a call of its own; on settings whose SecretG2 has Z = 1 and on settings that received Jacobian images"""
+    t0 = time.perf_counter()
+    rng = random.Random(34)
+    rows = padded_single_rows(S_TEST, 2 * 64 + 37)
+    rng.shuffle(rows)
+    cs, pis, xs, ys = vi.single_images(rows, rng)
+    want = [r[5] for r in rows]
+    t1 = time.perf_counter()
+    for ks in (ks16, ks16_jacobian):
+        got = ks.check_proof_single_batch(cs, pis, xs, ys)
+        bad = [(r[0], bool(g), r[5]) for r, g in zip(rows, got) if bool(g) != r[5]]
+        assert not bad, bad
+    lone = [i for i, r in enumerate(rows) if not r[0].startswith(("ordinary/", "pad"))]
+    assert len(lone) > 80
+    bad = []
+    for i in lone:
+        ks = ks16_jacobian if i % 2 else ks16
+        got = ks.check_proof_single_batch(cs[i:i + 1], pis[i:i + 1], xs[i:i + 1], ys[i:i + 1])
+        if [bool(g) for g in got] != [want[i]]:
+            bad.append((rows[i][0], list(got), want[i]))
+    assert not bad, bad
+    report("crafted single rows", t1 - t0, time.perf_counter() - t1)
+
+
+def test_crafted_multi_rows_on_the_device(kz, ks16, ks16_jacobian):
+    """every multi row of verify_cases, one call per length: powers of two, the lengths 3, 5, 12 that pin x^np against SecretG2[n], x = 0,
+    x = 1, x = s w"""
+    t0 = time.perf_counter()
+    rng = random.Random(35)
+    rows = vc.multi_rows(S_TEST, random.Random(2))
+    calls = []
+    for n in vc.MULTI_NS:
+        sub = [r for r in rows if r[5] == n]
+        rng.shuffle(sub)
+        cs = np.stack([vi.g1_scalar(r[1], rng.randrange(2, pr.P) if i % 2 else None) for i, r in enumerate(sub)])
+        pis = np.stack([vi.g1_scalar(r[2], None if i % 3 else rng.randrange(2, pr.P)) for i, r in enumerate(sub)])
+        calls.append((n, sub, cs, pis, ko.fr_from_ints([r[3] for r in sub]), np.stack([ko.fr_from_ints(r[4]) for r in sub])))
+    assert sum(len(c[1]) for c in calls) == len(rows)
+    t1 = time.perf_counter()
+    bad = []
+    for ks in (ks16, ks16_jacobian):
+        for n, sub, cs, pis, xs, yss in calls:
+            got = ks.check_proof_multi_batch(cs, pis, xs, yss)
+            bad += [(r[0], bool(g), r[6]) for r, g in zip(sub, got) if bool(g) != r[6]]
+    assert not bad, bad
+    report("crafted multi rows", t1 - t0, time.perf_counter() - t1)
+
+
+def fixture_g2_points():
+    fx = json.load(open(os.path.join(GOLDEN, "trusted_setup_g2.json")))
+    enc, pts, Q = [], [], pr.G2_GEN
+    for h in fx["setup_G2"]:
+        b = bytes.fromhex(h)
+        assert b == pr.g2_compress(Q)                       # the fixture holds [1337^i] G2
+        enc.append(b); pts.append(Q)
+        Q = pr.g2_mul(Q, 1337)
+    return enc, pts
+
+
+def test_g2_from_compressed_in_a_multi_wavefront_batch(kz):
+    """130 encodings (two wavefronts and a tail of 2) with the infinity encoding in the middle: every image is the reference point's; then one
+    bad encoding at row 0, 64 and 129 in turn fails the whole call"""
+    t0 = time.perf_counter()
+    enc, pts = fixture_g2_points()
+    enc, pts = enc + enc[::-1], pts + pts[::-1]
+    enc[70], pts[70] = bytes([0xc0]) + bytes(95), None
+    assert len(enc) == 130
+    outside = None
+    for x0 in range(1, 200):                                # on the curve, outside G2
+        x = (x0, 0)
+        y = pr.f2sqrt(pr.f2add(pr.f2mul(pr.f2sqr(x), x), pr.B2))
+        if y is not None and pr.g2_mul((x, y), pr.R) is not None:
+            outside = pr.g2_compress((x, y))
+            break
+    xp = bytearray(pr.P.to_bytes(48, "big") + bytes(48)); xp[0] |= 0x80              # x1 = p
+    bad_kinds = {0: bytes([0x40]) + bytes(95), 64: bytes(xp), 129: outside}
+    t1 = time.perf_counter()
+    fs = kz.FFTSettings(4)
+    got = fs.g2_from_compressed(np.frombuffer(b"".join(enc), dtype=np.uint8))
+    for i in range(130):
+        assert np.array_equal(got[i], vi.g2_kilic(pts[i])), i
+    assert np.array_equal(got[70], vi.g2_kilic(None))       # Kilic's Zero(): (0, 1, 0)
+    for row, b in bad_kinds.items():
+        spoiled = list(enc); spoiled[row] = b
+        with pytest.raises(kz.KzgError) as e:
+            fs.g2_from_compressed(np.frombuffer(b"".join(spoiled), dtype=np.uint8))
+        assert e.value.status == kz.ERR_BAD_POINT, row
+    fs.close()
+    report("g2_from_compressed x130", t1 - t0, time.perf_counter() - t1)
+
+
+@pytest.fixture(scope="module")
+def eth_fixture(kz):
+    enc, pts = fixture_g2_points()
+    fs = kz.FFTSettings(12)
+    lag = ko.g1_decompress(np.frombuffer(open(os.path.join(GOLDEN, "trusted_setup_g1_lagrange.bin"), "rb").read(), dtype=np.uint8))
+    eth = kz.EthSettings(fs, lag)
+    yield eth, pts
+    eth.close(); fs.close()
+
+
+def test_eth_crafted_and_byte_rows(kz, eth_fixture):
+    """the crafted rows compressed by the oracle and the byte-level rows on the fixture setup (s = 1337): 1 / 0 from the derived truth value,
+    2 / 3 in the reference's order of checks (z, y, commitment, proof); kzgSetupG2 as Z = 1 images, then as Jacobian images"""
+    t0 = time.perf_counter()
+    eth, pts = eth_fixture
+    rng = random.Random(4)
+    rows = vi.eth_rows(1337, rng)
+    want = [r[5] for r in rows]
+    assert set(want) == {0, 1, 2, 3}
+    c48, zs, ys, pi48 = vi.eth_arrays(rows)
+    t1 = time.perf_counter()
+    for jac in (False, True):
+        eth.set_setup_g2(np.stack([vi.g2_kilic(Q, vi.rand_fp2(rng) if jac else (1, 0)) for Q in pts]))
+        got = eth.verify_kzg_proof_batch(c48, zs, ys, pi48)
+        bad = [(r[0], int(g), r[5]) for r, g in zip(rows, got) if int(g) != r[5]]
+        assert not bad, bad
+    byte_rows = [i for i, r in enumerate(rows) if r[0].startswith("bytes/")]
+    for i in byte_rows:                                      # each byte-level row alone
+        got = eth.verify_kzg_proof_batch(c48[i:i + 1], zs[i:i + 1], ys[i:i + 1], pi48[i:i + 1])
+        assert list(got) == [want[i]], rows[i][0]
+    report("eth rows", t1 - t0, time.perf_counter() - t1)
+
+
+def test_g1_image_outside_the_subgroup_stays_in_its_row(kz, ks16):
+    """The order-3 point (0, 2) as pi, then as C, in one row of an ordinary batch (tests/test_pairing_host.py runs the same rows through the
+    host build under sanitizers first): the call succeeds and every other row's result is unchanged.  The row's own result is unspecified
+    (include/kzg_hip.h) and printed; on the host build it is False both times."""
+    rng = random.Random(5)
+    rows = [r for r in padded_single_rows(S_TEST, 2 * 64 + 37) if r[0].startswith(("ordinary/", "pad"))][:70]
+    cs, pis, xs, ys = vi.single_images(rows, rng)
+    want = [r[5] for r in rows]
+    evil = vi.g1_affine_image(*vi.ORDER3)
+    for what, k in (("pi", 2), ("C", 66)):
+        c2, p2 = cs.copy(), pis.copy()
+        (p2 if what == "pi" else c2)[k] = evil
+        got = [bool(g) for g in ks16.check_proof_single_batch(c2, p2, xs, ys)]      # raises unless the status is KZG_HIP_OK
+        assert got[:k] + got[k + 1:] == want[:k] + want[k + 1:], what
+        print("order-3 point as %s: the row returns %s" % (what, got[k]))

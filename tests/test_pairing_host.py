@@ -10,11 +10,18 @@ import numpy as np
 import pytest
 
 import pairing_ref as pr
+import verify_cases as vc
+import verify_images as vi
+from oracle import koracle as ko
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "host", "pairing_emul.cpp")
 OUT = os.path.join(HERE, "host", "_build", "libpairing_emul.so")
+OUT_SAN = os.path.join(HERE, "host", "_build", "pairing_emul_san")
+HEADERS = ("field.hpp", "g1.hpp", "tower.hpp", "g2.hpp", "pairing.hpp", "verify_inputs.hpp")
+S_TEST = 1927409816240961209460912649124
+S_ETH = 1337
 FIXTURE = os.path.join(HERE, "golden", "trusted_setup_g2.json")
 # the value the device computes: final_exponentiation raises to 3 (p^12 - 1) / r (pairing.hpp)
 DEVICE_EXP = 3 * pr.FINAL_EXP
@@ -24,11 +31,17 @@ DEVICE_EXP = 3 * pr.FINAL_EXP
 def pe():
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     inc = os.path.join(ROOT, "go-kzg_amd", "csrc")
-    deps = [SRC] + [os.path.join(inc, h) for h in ("field.hpp", "g1.hpp", "tower.hpp", "g2.hpp", "pairing.hpp")]
+    deps = [SRC] + [os.path.join(inc, h) for h in HEADERS]
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-I", inc, "-o", OUT, SRC])
     lib = C.CDLL(OUT)
-    lib.pe_pairing.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    vp = C.c_void_p
+    lib.pe_pairing.argtypes = [C.c_uint64, vp, vp, vp]
+    lib.pe_sizeof_prepared.restype = C.c_uint64
+    lib.pe_g2_prepare_kilic.argtypes = [vp, vp]
+    lib.pe_g2_kilic_to_affine.argtypes = [vp, vp]
+    lib.pe_kzg_check_batch.argtypes = [C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.pe_eth_check_batch.argtypes = [C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     return lib
 
 
@@ -193,3 +206,150 @@ def test_bilinearity_and_order(pe):
     assert chk(pr.g1_mul(G1, a), G2, nP, pr.g2_mul(G2, a)) == 1
     assert chk(pr.g1_mul(G1, a), G2, nP, pr.g2_mul(G2, a + 1)) == 0
     assert chk(None, G2, G1, None) == 1
+
+
+# ---------------- the check-input lanes (verify_inputs.hpp) on crafted rows, and G2 images with Z != 1 ----------------
+def prepared(pe, kilic):   # what k_g2_prepare leaves for one Kilic image (None: bls.GenG2)
+    buf = np.zeros(pe.pe_sizeof_prepared(), dtype=np.uint8)
+    img = None if kilic is None else np.ascontiguousarray(kilic)
+    pe.pe_g2_prepare_kilic(None if img is None else p(img), p(buf))
+    return buf
+
+
+def kzg_check(pe, gen, q1, cs, pis, bs, ys=None, es=None):
+    n = len(cs)
+    cs, pis, bs = (np.ascontiguousarray(a) for a in (cs, pis, bs))
+    ys = None if ys is None else np.ascontiguousarray(ys)
+    es = None if es is None else np.ascontiguousarray(es)
+    ok = np.zeros(n, dtype=np.uint8)
+    pe.pe_kzg_check_batch(n, p(cs), p(pis), None if ys is None else p(ys), None if es is None else p(es), p(bs), p(gen), p(q1), p(ok))
+    return [bool(v) for v in ok]
+
+
+@pytest.fixture(scope="module")
+def g2_s_test():
+    return pr.g2_mul(pr.G2_GEN, S_TEST % pr.R)
+
+
+def test_g2_jacobian_images(pe):
+    """(x Z^2, y Z^3, Z) through g2_from_kilic + g2_to_affine is the affine point, for Z in F_p, in u F_p, in general position and at p - 1;
+    Z = 0 is infinity whatever X and Y hold"""
+    rng = random.Random(21)
+    Q = pr.g2_mul(pr.G2_GEN, 0x123456789abcdef)
+    zs = [(1, 0), (rng.randrange(2, pr.P), 0), (0, rng.randrange(2, pr.P)), vi.rand_fp2(rng), vi.rand_fp2(rng), (pr.P - 1, pr.P - 1), (0, 1), (pr.P - 1, 0)]
+    for pt in (Q, pr.G2_GEN):
+        for z in zs:
+            img = vi.g2_kilic(pt, z)
+            if z != (1, 0):
+                assert not np.array_equal(img, vi.g2_kilic(pt))
+            out = np.zeros(48, dtype=np.uint32)
+            assert pe.pe_g2_kilic_to_affine(p(img), p(out)) == 0
+            v = ints(out)
+            assert ((v[0], v[1]), (v[2], v[3])) == pt, z
+    out = np.ones(48, dtype=np.uint32)
+    assert pe.pe_g2_kilic_to_affine(p(vi.g2_kilic(None)), p(out)) == 1 and not out.any()
+    junk = vi.g2_kilic(Q, vi.rand_fp2(rng)); junk[2] = 0           # X, Y arbitrary, Z = 0
+    assert pe.pe_g2_kilic_to_affine(p(junk), p(out)) == 1 and not out.any()
+
+
+def test_prepared_lines_do_not_depend_on_z(pe, g2_s_test):
+    rng = random.Random(22)
+    want = prepared(pe, vi.g2_kilic(g2_s_test))
+    for z in ((rng.randrange(2, pr.P), 0), (0, rng.randrange(2, pr.P)), vi.rand_fp2(rng), (pr.P - 1, pr.P - 1)):
+        assert np.array_equal(prepared(pe, vi.g2_kilic(g2_s_test, z)), want), z
+    assert np.array_equal(prepared(pe, None), prepared(pe, vi.g2_kilic(pr.G2_GEN, vi.rand_fp2(rng))))
+    assert not np.array_equal(prepared(pe, None), want)
+
+
+def test_crafted_single_rows(pe, g2_s_test):
+    """every row of verify_cases.single_rows through the lane of k_kzg_check_inputs and the two-pair check: ok == the derived truth value;
+    [s] G2 arrives as a Jacobian image, C and pi alternate between Z = 1 and Z != 1"""
+    rng = random.Random(1)
+    rows = vc.single_rows(S_TEST, rng)
+    gen, q1 = prepared(pe, None), prepared(pe, vi.g2_kilic(g2_s_test, vi.rand_fp2(rng)))
+    cs, pis, xs, ys = vi.single_images(rows, rng)
+    got = kzg_check(pe, gen, q1, cs, pis, xs, ys=ys)
+    bad = [(r[0], g, r[5]) for r, g in zip(rows, got) if g != r[5]]
+    assert not bad, bad
+
+
+def test_crafted_multi_rows(pe):
+    """every row of verify_cases.multi_rows with [I'(s)] G1 supplied as a point and b = x^np: the G1 side pairs with SecretG2[n], n = len(ys)"""
+    rng = random.Random(2)
+    s = S_TEST % pr.R
+    rows = vc.multi_rows(s, rng)
+    gen = prepared(pe, None)
+    bad = []
+    for n in vc.MULTI_NS:
+        sub = [r for r in rows if r[5] == n]
+        assert sub
+        qn = prepared(pe, vi.g2_kilic(pr.g2_mul(pr.G2_GEN, pow(s, n, pr.R)), vi.rand_fp2(rng)))
+        cs = np.stack([vi.g1_scalar(r[1], rng.randrange(2, pr.P) if i % 2 else None) for i, r in enumerate(sub)])
+        pis = np.stack([vi.g1_scalar(r[2], None if i % 3 else rng.randrange(2, pr.P)) for i, r in enumerate(sub)])
+        es = np.stack([vi.g1_scalar(vc.interp_at(r[4], r[3], s), rng.randrange(2, pr.P) if i % 4 == 1 else None) for i, r in enumerate(sub)])
+        bs = ko.fr_from_ints([pow(r[3], vc.next_pow2(n), pr.R) for r in sub])
+        got = kzg_check(pe, gen, qn, cs, pis, bs, es=es)
+        bad += [(r[0], g, r[6]) for r, g in zip(sub, got) if g != r[6]]
+    assert not bad, bad
+
+
+def test_eth_rows(pe):
+    """the crafted rows compressed, and the byte-level rows, through the lane of k_eth_check_inputs on the fixture setup's secret: 1 / 0 from
+    the derived truth value, 2 / 3 in the reference's order of checks"""
+    rng = random.Random(4)
+    rows = vi.eth_rows(S_ETH, rng)
+    fx = json.load(open(FIXTURE))
+    g2s = pr.g2_decompress(bytes.fromhex(fx["setup_G2"][1]))
+    assert g2s == pr.g2_mul(pr.G2_GEN, S_ETH)
+    gen, q1 = prepared(pe, None), prepared(pe, vi.g2_kilic(g2s))
+    c48, zs, ys, pi48 = vi.eth_arrays(rows)
+    res = np.zeros(len(rows), dtype=np.uint8)
+    pe.pe_eth_check_batch(len(rows), p(c48), p(zs), p(ys), p(pi48), p(gen), p(q1), p(res))
+    bad = [(r[0], int(g), r[5]) for r, g in zip(rows, res) if g != r[5]]
+    assert not bad, bad
+    assert {r[5] for r in rows} == {0, 1, 2, 3}
+
+
+@pytest.fixture(scope="module")
+def pe_san():   # the same source as a program with the address and undefined-behaviour sanitizers
+    inc = os.path.join(ROOT, "go-kzg_amd", "csrc")
+    deps = [SRC] + [os.path.join(inc, h) for h in HEADERS]
+    os.makedirs(os.path.dirname(OUT_SAN), exist_ok=True)
+    if not os.path.exists(OUT_SAN) or any(os.path.getmtime(d) > os.path.getmtime(OUT_SAN) for d in deps):
+        # -O0: a third of the build time of -O1 with the sanitizers on these always-inline bodies.  shift-base is off: the divsteps of inv<>()
+        # (field.hpp) double a negative int32 with `<< 1`, which C++20 defines as every compiler has always computed it; shift counts stay checked
+        subprocess.check_call(["g++", "-O0", "-g", "-std=c++17", "-DPE_MAIN", "-fsanitize=address,undefined", "-fno-sanitize=shift-base",
+                               "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-I", inc, "-o", OUT_SAN, SRC])
+    return OUT_SAN
+
+
+def test_g1_image_outside_the_subgroup_stays_in_its_row(pe, pe_san, g2_s_test, tmp_path):
+    """check_proof_*_batch and pairings_verify_batch take G1 images unchecked, and the lane multiplies pi with the GLV schedule, which assumes
+    membership in G1.  One row of an ordinary batch holds the order-3 point (0, 2) as pi, then as C: under the sanitizers the lane terminates,
+    reads and writes nothing out of bounds, and every other row's result is unchanged.  What the row itself returns is unspecified
+    (include/kzg_hip.h); it is printed, and the host library and the sanitizer build agree on it."""
+    rng = random.Random(5)
+    rows = [r for r in vc.single_rows(S_TEST, rng) if r[0].startswith("ordinary/")][:8]
+    cs, pis, xs, ys = vi.single_images(rows, rng)
+    q1_img = vi.g2_kilic(g2_s_test)
+    gen, q1 = prepared(pe, None), prepared(pe, q1_img)
+    want = [r[5] for r in rows]
+    assert True in want and False in want
+    evil = vi.g1_affine_image(*vi.ORDER3)
+    for what, k in (("pi", 2), ("C", 5)):
+        c2, p2 = cs.copy(), pis.copy()
+        (p2 if what == "pi" else c2)[k] = evil
+        path = tmp_path / ("batch_%s.bin" % what)
+        with open(path, "wb") as f:
+            f.write(np.uint64(len(rows)).tobytes())
+            for a in (c2, p2, ys, xs, q1_img):
+                f.write(np.ascontiguousarray(a).tobytes())
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
+        run = subprocess.run([pe_san, str(path)], capture_output=True, text=True, timeout=300, env=env)
+        assert run.returncode == 0 and not run.stderr.strip(), run.stderr[-2000:]
+        got = [ch == "1" for ch in run.stdout.strip()]
+        assert len(got) == len(rows)
+        assert got[:k] + got[k + 1:] == want[:k] + want[k + 1:], (what, got, want)
+        lib_got = kzg_check(pe, gen, q1, c2, p2, xs, ys=ys)
+        assert lib_got == got
+        print("order-3 point as %s: the row returns %s" % (what, got[k]))
