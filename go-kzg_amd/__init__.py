@@ -97,6 +97,8 @@ def lib():
         "kzg_hip_kzg_set_secret_g2": (i32, [vp, vp, u64]), "kzg_hip_check_proof_single_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "kzg_hip_check_proof_multi_batch": (i32, [vp, vp, vp, vp, vp, u64, u64, vp]),
         "kzg_hip_eth_set_setup_g2": (i32, [vp, vp, u64]), "kzg_hip_eth_verify_kzg_proof_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
+        "kzg_hip_eth_verify_aggregate_kzg_proof_batch": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "kzg_hip_test_sha256_lanes": (i32, [vp, vp, vp, vp, u64, vp]), "kzg_hip_test_hash_to_bls_field_lanes": (i32, [vp, vp, u64, vp]),
         "kzg_hip_pairing_test": (i32, [vp, vp, vp, u64, vp]),
         "kzg_hip_toeplitz_part2": (i32, [vp, vp, vp, u64, vp]), "kzg_hip_toeplitz_part3": (i32, [vp, vp, u64, vp]),
         "kzg_hip_fk20_single_settings_new": (i32, [vp, u64, pp]), "kzg_hip_fk20_single_settings_free": (None, [vp]),
@@ -976,6 +978,25 @@ class EthSettings:
         out = np.zeros(n, dtype=np.uint8)
         _chk(lib().kzg_hip_eth_verify_kzg_proof_batch(self.h, _p(c), _p(zs), _p(ys), _p(pi), n, _p(out)))
         return out
+
+    def verify_aggregate_kzg_proof_batch(self, blobs, counts, commitments, proofs, intermediates=False):
+        """eth.VerifyAggregateKZGProof (eth/eth.go:155-172) over many sidecars: `counts[j]` blobs (0 is valid) of the (sum(counts), n, 32) uint8 blobs and of
+        the (sum(counts), 48) expected commitments belong to sidecar j, proofs is (sidecars, 48) -> uint8 codes: 1 valid, 0 the pairing check failed, 2 a
+        field element of the block not below r, 3 a commitment or the proof not a valid G1 encoding.  intermediates=True: also the aggregated
+        commitments (sidecars, 48), z and y (sidecars, 4) of every sidecar (unspecified where the code is 2 or 3)"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        s, total = counts.shape[0], int(counts.sum(dtype=object)) if counts.shape[0] else 0
+        blobs = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(-1, self.n, 32)
+        comm = np.ascontiguousarray(commitments, dtype=np.uint8).reshape(-1, 48)
+        pi = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, 48)
+        if blobs.shape[0] != total or comm.shape[0] != total or pi.shape[0] != s:
+            raise KzgError(ERR_LEN_MISMATCH, "sum(counts) blobs and commitments, one proof per sidecar")
+        out = np.zeros(s, dtype=np.uint8)
+        c48, zs, ys = (np.zeros((s, 48), dtype=np.uint8), fr_empty(s), fr_empty(s)) if intermediates else (None, None, None)
+        _chk(lib().kzg_hip_eth_verify_aggregate_kzg_proof_batch(self.h, _p(blobs), _p(counts), _p(comm), _p(pi), s, _p(out),
+                                                                _p(c48) if intermediates else None, _p(zs) if intermediates else None,
+                                                                _p(ys) if intermediates else None))
+        return (out, c48, zs, ys) if intermediates else out
 
     def evaluate_polynomial_in_evaluation_form(self, polynomial, x):
         """eth.EvaluatePolynomialInEvaluationForm (eth/helpers.go:207-211)"""

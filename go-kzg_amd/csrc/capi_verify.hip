@@ -3,6 +3,7 @@
 // check is one lane's work and stays on Kilic in the Go shim.
 #include "capi_common.hpp"
 #include "pairing.hpp"
+#include "sha256_lane.hpp"
 
 // G2 points a handle verifies against: the caller's array (Kilic images) and its prepared points, [1]G2 and [s]G2 at once, [s^n]G2 on first use.
 // Thread safety: the handle's pointer to its state is read and replaced under the handle's g2_mu (g2_of / g2_state_set); every check holds its
@@ -239,6 +240,166 @@ int kzg_hip_eth_verify_kzg_proof_batch(kzg_hip_eth *eth, const void *commitments
     HIPCHK(hipMemcpyAsync(result, d_ok.p, count, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     for (uint64_t i = 0; i < count; i++) if (st[i]) result[i] = st[i];
+    return KZG_HIP_OK;
+    KZG_CATCH
+}
+
+// eth.VerifyAggregateKZGProof (eth/eth.go:155-172) over many sidecars.  Per chunk of whole sidecars: ONE upload of the raw bytes, then
+// transcripts -> aggregated polynomials (BlobsToPolynomials + PolyLinComb) -> aggregated commitments (FromCompressedG1, the powers, a
+// segmented sum) -> y (the quotient kernel's evaluation half) -> the check inputs and the pairing; one download of the results.  A verifier
+// commits to nothing: no fixed-base table is built or walked.
+int kzg_hip_eth_verify_aggregate_kzg_proof_batch(kzg_hip_eth *eth, const void *blobs_le32, const uint64_t *blob_counts, const void *commitments48,
+                                                 const void *proofs48, uint64_t sidecars, uint8_t *result,
+                                                 void *out_agg_commitments48, void *out_zs_fr, void *out_ys_fr) {
+    if (!eth) return KZG_HIP_ERR_BAD_ARG;
+    KZG_TRY
+    const std::shared_ptr<g2_state> g = g2_of(eth->g2_mu, eth->g2);
+    if (!g) return KZG_HIP_ERR_BAD_ARG;
+    if (!sidecars) return KZG_HIP_OK;
+    if (!blob_counts || !proofs48 || !result) return KZG_HIP_ERR_BAD_ARG;
+    const uint64_t n = eth->n;
+    uint64_t total = 0;
+    for (uint64_t j = 0; j < sidecars; j++) {
+        if (blob_counts[j] > UINT64_MAX - total) return KZG_HIP_ERR_TOO_WIDE;
+        total += blob_counts[j];
+    }
+    if (total > (UINT64_MAX >> 1) / (n * 32)) return KZG_HIP_ERR_TOO_WIDE;      // (the byte offsets must not overflow either)
+    if (total && (!blobs_le32 || !commitments48)) return KZG_HIP_ERR_BAD_ARG;
+    // where the transcripts are hashed: the device takes the same 28 ms for 1 or 4096 chains of four blobs, a host thread 0.23 ms per such
+    // sidecar: the measured curves cross between 128 and 192 sidecars (profiles/verify_aggregate.md)
+    const char *tenv = getenv("KZG_HIP_ETH_TRANSCRIPT");                          // read per call: a measurement switches between the two in one process
+    const int forced = !tenv ? 0 : !strcmp(tenv, "host") ? 1 : !strcmp(tenv, "device") ? 2 : 0;
+    constexpr uint64_t TRANSCRIPT_DEVICE_FROM = 176;
+    const bool on_device = forced ? forced == 2 : sidecars >= TRANSCRIPT_DEVICE_FROM;
+    const char *cenv = getenv("KZG_HIP_ETH_VERIFY_CHUNK_MB");                    // (fractions allowed: tests force chunks of a few small blobs)
+    const double cmb = cenv ? atof(cenv) : 0.0;
+    const uint64_t budget = (uint64_t)((cmb > 0.0 ? cmb : 4096.0) * 1048576.0);
+    constexpr uint64_t CHECKS = 8192;                                            // per pairing launch, as kzg_hip_pairings_verify_batch
+    const uint8_t *blobs = (const uint8_t *)blobs_le32, *comms = (const uint8_t *)commitments48, *proofs = (const uint8_t *)proofs48;
+
+    stream_lease lease(eth->fs);
+    hipStream_t s = lease.s;
+    std::vector<uint64_t> off; std::vector<fr> h_r, h_z; std::vector<uint8_t> st;
+    drain_on_exit drain(s);                                                      // declared after the host buffers the stream copies from / into
+    uint64_t j0 = 0, b0 = 0;
+    while (j0 < sidecars) {
+        // the chunk: whole sidecars while their blobs fit the byte budget (a larger sidecar forms a chunk by itself), at most CHECKS of them
+        off.assign(1, 0);
+        uint64_t j1 = j0;
+        while (j1 < sidecars && j1 - j0 < CHECKS) {
+            const uint64_t nb = off.back() + blob_counts[j1];
+            if (j1 > j0 && nb * n * 32 > budget) break;
+            off.push_back(nb); j1++;
+        }
+        const uint64_t S = j1 - j0, B = off.back();
+        const uint8_t *c_blobs = blobs + b0 * n * 32, *c_comms = comms + b0 * 48;
+        dtmp<uint8_t> d_blobs(s), d_comm(s), d_pi48(s), d_cbad(s), d_pbad(s), d_st(s), d_ok(s), d_c48(s);
+        dtmp<uint64_t> d_off(s); dtmp<fr> d_r(s), d_z(s), d_y(s), d_agg(s), d_q(s), d_pow(s); dtmp<uint32_t> d_flag(s);
+        dtmp<g1j> d_cpts(s), d_cmul(s), d_sum(s), d_sumk(s), d_pik(s), d_p0(s), d_p1(s);
+        const uint64_t extra = eth_quotient_scratch_elems(n, S);
+        CHK(d_blobs.alloc(B * n * 32)); CHK(d_comm.alloc(B * 48)); CHK(d_pi48.alloc(S * 48)); CHK(d_cbad.alloc(B)); CHK(d_pbad.alloc(S)); CHK(d_st.alloc(S));
+        CHK(d_ok.alloc(S)); CHK(d_off.alloc(S + 1)); CHK(d_r.alloc(S)); CHK(d_z.alloc(S)); CHK(d_y.alloc(S)); CHK(d_agg.alloc(S * n)); CHK(d_q.alloc(S * n + extra));
+        CHK(d_pow.alloc(B)); CHK(d_flag.alloc(S)); CHK(d_cpts.alloc(B)); CHK(d_cmul.alloc(B)); CHK(d_sum.alloc(S)); CHK(d_sumk.alloc(S)); CHK(d_pik.alloc(S));
+        CHK(d_p0.alloc(S)); CHK(d_p1.alloc(S));
+        HIPCHK(hipMemsetAsync(d_st.p, 0, S, s));
+        HIPCHK(hipMemsetAsync(d_flag.p, 0, S * 4, s));
+        HIPCHK(hipMemcpyAsync(d_off.p, off.data(), (S + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_pi48.p, proofs + 48 * j0, S * 48, hipMemcpyHostToDevice, s));
+        if (B) {
+            HIPCHK(hipMemcpyAsync(d_comm.p, c_comms, B * 48, hipMemcpyHostToDevice, s));
+            CHK(h2d_copy(d_blobs.p, c_blobs, B * n * 32, s));
+        }
+        launch_g1_decompress_rows(s, d_comm.p, d_cpts.p, B, d_cbad.p, false);   // FromCompressedG1(commitments), eth/helpers.go:149-157
+        launch_g1_decompress_rows(s, d_pi48.p, d_pik.p, S, d_pbad.p, true);     // ... and of the proofs (eth/eth.go:168-170)
+        if (on_device) {
+            launch_eth_transcripts(s, d_blobs.p, d_comm.p, d_off.p, n, S, d_r.p, d_z.p);
+        } else {
+            // the existing host chain (sha256.cpp) on the calling thread, while the device decompresses
+            h_r.resize(S); h_z.resize(S);
+            for (uint64_t j = 0; j < S; j++) {
+                const uint64_t cnt = off[j + 1] - off[j];
+                sha256 h;
+                h.update("FSBLOBVERIFY_V1_", 16);
+                h.update_u64_le(n);
+                h.update_u64_le(cnt);
+                if (cnt) { h.update(c_blobs + off[j] * n * 32, cnt * n * 32); h.update(c_comms + off[j] * 48, cnt * 48); }
+                uint8_t tr[33], d[32];
+                h.final(tr);
+                for (int tag = 0; tag < 2; tag++) {
+                    tr[32] = (uint8_t)tag;
+                    sha256 h2;
+                    h2.update(tr, 33);
+                    h2.final(d);
+                    (tag ? h_z : h_r)[j] = fr_from_digest_bytes(d);
+                }
+            }
+            HIPCHK(hipMemcpyAsync(d_r.p, h_r.data(), S * sizeof(fr), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_z.p, h_z.data(), S * sizeof(fr), hipMemcpyHostToDevice, s));
+        }
+        launch_eth_agg_poly(s, d_blobs.p, d_off.p, d_r.p, n, S, d_agg.p, d_st.p);
+        launch_eth_powers(s, d_r.p, d_off.p, S, d_pow.p);
+        launch_g1_mul_vec(s, d_cpts.p, B ? B : 1, d_pow.p, 1, B, d_cmul.p);     // LinCombG1(commitments, powers), eth/helpers.go:158-160
+        launch_g1_segment_sum(s, d_cmul.p, d_cbad.p, d_off.p, S, d_sum.p, d_sumk.p, d_st.p);
+        // y = EvaluatePolynomialInEvaluationForm(aggregatedPoly, z) (eth/eth.go:166): the quotient kernel's first half
+        launch_eth_quotient(s, d_agg.p, n, eth->d_domain, n, S, d_z.p, 1, eth->fs->d_inv_pow2 + ilog2(n), d_q.p, d_y.p, d_flag.p, 1, extra ? d_q.p + S * n : nullptr);
+        launch_eth_agg_finish(s, d_flag.p, d_pbad.p, S, d_y.p, d_st.p);
+        // VerifyKZGProofFromPoints (eth/helpers.go:55-68): e(C - [y]G1 + [z] pi, G2) e(-pi, kzgSetupG2[1]) == 1
+        launch_kzg_check_inputs(s, d_sumk.p, d_pik.p, d_y.p, nullptr, d_z.p, S, d_p0.p, d_p1.p);
+        launch_pairing_check(s, true, g->d_gen, g->d_s, d_p0.p, d_p1.p, S, d_ok.p);
+        if (out_agg_commitments48) {
+            CHK(d_c48.alloc(S * 48));
+            launch_g1_compress(s, d_sum.p, d_c48.p, S);
+        }
+        HIPCHK(hipGetLastError());
+        st.resize(S);
+        HIPCHK(hipMemcpyAsync(st.data(), d_st.p, S, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(result + j0, d_ok.p, S, hipMemcpyDeviceToHost, s));
+        if (out_agg_commitments48) HIPCHK(hipMemcpyAsync((uint8_t *)out_agg_commitments48 + 48 * j0, d_c48.p, S * 48, hipMemcpyDeviceToHost, s));
+        if (out_zs_fr) HIPCHK(hipMemcpyAsync((fr *)out_zs_fr + j0, d_z.p, S * sizeof(fr), hipMemcpyDeviceToHost, s));
+        if (out_ys_fr) HIPCHK(hipMemcpyAsync((fr *)out_ys_fr + j0, d_y.p, S * sizeof(fr), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (uint64_t j = 0; j < S; j++) if (st[j]) result[j0 + j] = st[j];
+        j0 = j1; b0 += B;
+    }
+    return KZG_HIP_OK;
+    KZG_CATCH
+}
+
+// test hooks (kzg_hip_internal.h): the transcript kernel's hash and reduction, one message / digest per lane
+int kzg_hip_test_sha256_lanes(kzg_hip_fft *fs, const void *data, const uint64_t *offsets, const uint64_t *lens, uint64_t rows, void *out32) {
+    if (!fs || (rows && (!offsets || !lens || !out32))) return KZG_HIP_ERR_BAD_ARG;
+    if (!rows) return KZG_HIP_OK;
+    KZG_TRY
+    uint64_t bytes = 0;
+    for (uint64_t t = 0; t < rows; t++) bytes = std::max(bytes, offsets[t] + lens[t]);
+    if (bytes && !data) return KZG_HIP_ERR_BAD_ARG;
+    stream_lease lease(fs);
+    hipStream_t s = lease.s;
+    dtmp<uint8_t> d_data(s); dtmp<uint64_t> d_off(s), d_len(s); dtmp<uint32_t> d_out(s);
+    CHK(d_data.alloc(bytes)); CHK(d_off.alloc(rows)); CHK(d_len.alloc(rows)); CHK(d_out.alloc(8 * rows));
+    if (bytes) HIPCHK(hipMemcpyAsync(d_data.p, data, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_off.p, offsets, rows * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_len.p, lens, rows * 8, hipMemcpyHostToDevice, s));
+    launch_test_sha256_lanes(s, d_data.p, d_off.p, d_len.p, rows, d_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out32, d_out.p, 32 * rows, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return KZG_HIP_OK;
+    KZG_CATCH
+}
+int kzg_hip_test_hash_to_bls_field_lanes(kzg_hip_fft *fs, const void *digests32, uint64_t rows, void *out_fr) {
+    if (!fs || (rows && (!digests32 || !out_fr))) return KZG_HIP_ERR_BAD_ARG;
+    if (!rows) return KZG_HIP_OK;
+    KZG_TRY
+    stream_lease lease(fs);
+    hipStream_t s = lease.s;
+    dtmp<uint8_t> d_in(s); dtmp<fr> d_out(s);
+    CHK(d_in.alloc(32 * rows)); CHK(d_out.alloc(rows));
+    HIPCHK(hipMemcpyAsync(d_in.p, digests32, 32 * rows, hipMemcpyHostToDevice, s));
+    launch_test_hash_to_bls_field_lanes(s, d_in.p, rows, d_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_fr, d_out.p, rows * sizeof(fr), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return KZG_HIP_OK;
     KZG_CATCH
 }

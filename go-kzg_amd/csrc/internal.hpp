@@ -151,6 +151,24 @@ void launch_eth_check_inputs(hipStream_t s, const uint8_t *c48, const uint8_t *z
 void launch_pairing_check(hipStream_t s, bool shared_lines, const g2_prepared *q0, const g2_prepared *q1, const g1j *p0, const g1j *p1, uint64_t n, uint8_t *ok);
 void launch_pairing_value(hipStream_t s, const g1j *g1_kilic, const g2_prepared *q, uint64_t n, fp *out);   // test hook: reduced e(g1[i], Q_i), standard form
 
+// ---------------- k_eth_aggregate.hip ----------------
+// eth.VerifyAggregateKZGProof over a chunk of sidecars: off[j] .. off[j + 1] (sidecars + 1 entries) are sidecar j's blobs and commitments
+// within the chunk's raw bytes (blobs: n x 32 little-endian bytes each; comms: 48 bytes each).  Challenges and powers are Montgomery images.
+void launch_eth_transcripts(hipStream_t s, const uint8_t *blobs, const uint8_t *comms, const uint64_t *off, uint64_t n, uint64_t sidecars, fr *r_out, fr *z_out);
+// agg[j][i] = sum_k r_j^k blob_(j,k)[i]; status[j] = 2 where an element of the sidecar is not below r (status is otherwise left alone)
+void launch_eth_agg_poly(hipStream_t s, const uint8_t *blobs, const uint64_t *off, const fr *r, uint64_t n, uint64_t sidecars, fr *agg, uint8_t *status);
+void launch_eth_powers(hipStream_t s, const fr *r, const uint64_t *off, uint64_t sidecars, fr *pow);   // pow[off[j] + k] = r_j^k
+// launch_g1_decompress with bad[row] = 0 / 1 per row; device-internal images, or Kilic images when to_kilic
+void launch_g1_decompress_rows(hipStream_t s, const uint8_t *in48, g1j *out, uint64_t n, uint8_t *bad, bool to_kilic);
+// out[j] = sum of pts[off[j] .. off[j + 1]) (device-internal; none: inf), out_kilic[j] its Kilic image; status[j] = 3 where one of the
+// sidecar's pt_bad is set and status[j] was 0
+void launch_g1_segment_sum(hipStream_t s, const g1j *pts, const uint8_t *pt_bad, const uint64_t *off, uint64_t sidecars, g1j *out, g1j *out_kilic, uint8_t *status);
+// y[j] = 0 where z_in_domain[j]; status[j] = 3 where proof_bad[j] and status[j] was 0
+void launch_eth_agg_finish(hipStream_t s, const uint32_t *z_in_domain, const uint8_t *proof_bad, uint64_t sidecars, fr *y, uint8_t *status);
+// test hooks: SHA-256 of rows messages data[offsets[t] .. + lens[t]) and hashToBLSField's reduction of rows digests, one per lane
+void launch_test_sha256_lanes(hipStream_t s, const uint8_t *data, const uint64_t *offsets, const uint64_t *lens, uint64_t rows, uint32_t *out);
+void launch_test_hash_to_bls_field_lanes(hipStream_t s, const uint8_t *digests, uint64_t rows, fr *out);
+
 // profiling hook (HIP events around the dominant kernel), see capi.hip
 void prof_begin(hipStream_t s, const char *name);
 void prof_end(hipStream_t s, const char *name);

@@ -47,6 +47,11 @@ int kzg_hip_lincomb_promotions(kzg_hip_fft *fs, uint64_t *promoted, uint64_t *se
 int kzg_hip_test_fr_inv(kzg_hip_fft *fs, const void *in_fr, uint64_t n, void *out_coop, void *out_lane, void *out_block);
 /* test hook: SHA-256 of a host buffer through the transcript's implementation (x86 SHA extensions or the portable loop; no device needed) */
 void kzg_hip_test_sha256(const void *data, uint64_t len, void *out32);
+/* test hooks of the block verifier's transcript kernel (k_eth_aggregate.hip, sha256_lane.hpp): the SHA-256 digests of `rows` messages
+ * data[offsets[t] .. offsets[t] + lens[t]) hashed ON THE DEVICE, one message per lane of one launch (out32: rows x 32 bytes), and
+ * hashToBLSField's reduction of `rows` given 32-byte digests (read as little-endian integers, reduced mod r; out_fr: rows Fr) */
+int kzg_hip_test_sha256_lanes(kzg_hip_fft *fs, const void *data, const uint64_t *offsets, const uint64_t *lens, uint64_t rows, void *out32);
+int kzg_hip_test_hash_to_bls_field_lanes(kzg_hip_fft *fs, const void *digests32, uint64_t rows, void *out_fr);
 
 /* test hook of the pairing (k_pairing.hip): out_fp12[i] = e(g1[i], g2[i]) raised to 3 (p^12 - 1) / r (the exponent of pairing.hpp's final
  * exponentiation), 12 F_p elements of 48 bytes each in STANDARD form, order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1; G1 / G2 Kilic images in */

@@ -1,8 +1,9 @@
 //go:build kzg_hip && !bignum_pure && !bignum_hol256 && !bignum_hbls
 // +build kzg_hip,!bignum_pure,!bignum_hol256,!bignum_hbls
 
-// eth.VerifyKZGProofBatch: eth.VerifyKZGProof (eth/eth.go:114-135) over many proofs in one device call.  A lone VerifyKZGProof (and through
-// it PointEvaluationPrecompile, VerifyAggregateKZGProof, ValidateBlobsSidecar) stays on Kilic (INTEGRATION.md).
+// eth.VerifyKZGProofBatch: eth.VerifyKZGProof (eth/eth.go:114-135) over many proofs in one device call, and VerifyAggregateKZGProofBatch /
+// ValidateBlobsSidecarBatch: the block-level verifier (eth/eth.go:155-208) over many sidecars in one device call.  A lone VerifyKZGProof (and
+// through it PointEvaluationPrecompile) and the pairing of a lone VerifyAggregateKZGProof / ValidateBlobsSidecar stay on Kilic (INTEGRATION.md).
 package eth
 
 /*
@@ -12,8 +13,12 @@ package eth
 import "C"
 
 import (
+	"errors"
+	"fmt"
 	"sync"
 	"unsafe"
+
+	"github.com/protolambda/go-kzg/bls"
 )
 
 // the eth handle that has received kzgSetupG2 (kzg_hip_eth_set_setup_g2); CloseHip (eth_hip.go) clears it with the handle
@@ -59,4 +64,115 @@ func VerifyKZGProofBatch(commitments []KZGCommitment, zs, ys [][32]byte, proofs 
 		}
 	}
 	return oks, errs
+}
+
+// VerifyAggregateKZGProofBatch: (ok[j], errs[j]) = VerifyAggregateKZGProof(blobs[j], expectedKZGCommitments[j], proofs[j]) (eth/eth.go:155-172)
+// for many blocks in one device call: transcripts, aggregation, evaluation and the pairing all run there.  A block without blobs is valid input.
+func VerifyAggregateKZGProofBatch(blobs []BlobSequence, expectedKZGCommitments []KZGCommitmentSequence, proofs []KZGProof) ([]bool, []error) {
+	s := len(blobs)
+	if len(expectedKZGCommitments) != s || len(proofs) != s {
+		panic("VerifyAggregateKZGProofBatch: slices of different lengths")
+	}
+	oks, errs := make([]bool, s), make([]error, s)
+	if s == 0 {
+		return oks, errs
+	}
+	counts := make([]uint64, s)
+	total := 0
+	for j := range blobs {
+		if expectedKZGCommitments[j].Len() != blobs[j].Len() {
+			panic("got LinCombG1 numbers/factors length mismatch") // what the reference does here: bls.LinCombG1's panic (eth/helpers.go:159)
+		}
+		counts[j] = uint64(blobs[j].Len())
+		total += blobs[j].Len()
+	}
+	flat := make([]Blob, total)
+	comms := make([]KZGCommitment, total)
+	at := 0
+	for j := range blobs {
+		for i := 0; i < blobs[j].Len(); i++ {
+			flat[at] = blobs[j].At(i)
+			comms[at] = expectedKZGCommitments[j].At(i)
+			at++
+		}
+	}
+	var bp, cp unsafe.Pointer
+	if total > 0 {
+		bp, cp = unsafe.Pointer(&flat[0]), unsafe.Pointer(&comms[0])
+	}
+	hipSetupG2Mu.Lock()
+	if hipSetupG2For != hipEth {
+		if st := C.kzg_hip_eth_set_setup_g2(hipEth, unsafe.Pointer(&kzgSetupG2[0]), C.uint64_t(len(kzgSetupG2))); st != C.KZG_HIP_OK {
+			hipSetupG2Mu.Unlock()
+			panic("kzg_hip: eth_set_setup_g2 failed")
+		}
+		hipSetupG2For = hipEth
+	}
+	hipSetupG2Mu.Unlock()
+	res := make([]uint8, s)
+	if st := C.kzg_hip_eth_verify_aggregate_kzg_proof_batch(hipEth, bp, (*C.uint64_t)(unsafe.Pointer(&counts[0])), cp, unsafe.Pointer(&proofs[0]),
+		C.uint64_t(s), (*C.uint8_t)(unsafe.Pointer(&res[0])), nil, nil, nil); st != C.KZG_HIP_OK {
+		panic(fmt.Sprintf("kzg_hip: eth_verify_aggregate_kzg_proof_batch: status %d", int(st)))
+	}
+	for j, r := range res {
+		switch r {
+		case 1:
+			oks[j] = true
+		case 2:
+			errs[j] = errors.New("could not convert blobs to polynomials")
+		case 3:
+			// invalid encodings (the cold path): the reference's own parsing on the CPU names the input, in its order (eth/helpers.go:153-156, eth/eth.go:166-169)
+			for i := 0; i < expectedKZGCommitments[j].Len() && errs[j] == nil; i++ {
+				c := expectedKZGCommitments[j].At(i)
+				_, errs[j] = bls.FromCompressedG1(c[:])
+			}
+			if errs[j] == nil {
+				if _, err := bls.FromCompressedG1(proofs[j][:]); err != nil {
+					errs[j] = fmt.Errorf("failed to decode kzgProof: %v", err)
+				}
+			}
+			if errs[j] == nil {
+				panic("kzg_hip: eth_verify_aggregate_kzg_proof_batch rejected inputs that the reference's parsing accepts")
+			}
+		}
+	}
+	return oks, errs
+}
+
+// ValidateBlobsSidecarBatch: errs[j] = ValidateBlobsSidecar(slots[j], beaconBlockRoots[j], expectedKZGCommitments[j], blobsSidecars[j])
+// (eth/eth.go:185-208).  The slot, root and length checks run per row on the host; the rows that pass them share one device call.
+func ValidateBlobsSidecarBatch(slots []Slot, beaconBlockRoots []Root, expectedKZGCommitments []KZGCommitmentSequence, blobsSidecars []BlobsSidecar) []error {
+	s := len(blobsSidecars)
+	if len(slots) != s || len(beaconBlockRoots) != s || len(expectedKZGCommitments) != s {
+		panic("ValidateBlobsSidecarBatch: slices of different lengths")
+	}
+	errs := make([]error, s)
+	var rows []int
+	var blobs []BlobSequence
+	var comms []KZGCommitmentSequence
+	var proofs []KZGProof
+	for j, sc := range blobsSidecars {
+		switch {
+		case slots[j] != sc.BeaconBlockSlot:
+			errs[j] = fmt.Errorf("slot doesn't match sidecar's beacon block slot (%v != %v)", slots[j], sc.BeaconBlockSlot)
+		case beaconBlockRoots[j] != sc.BeaconBlockRoot:
+			errs[j] = errors.New("roots not equal")
+		case sc.Blobs.Len() != expectedKZGCommitments[j].Len():
+			errs[j] = fmt.Errorf("blob len doesn't match expected kzg commitments len (%v != %v)", sc.Blobs.Len(), expectedKZGCommitments[j].Len())
+		default:
+			rows = append(rows, j)
+			blobs = append(blobs, sc.Blobs)
+			comms = append(comms, expectedKZGCommitments[j])
+			proofs = append(proofs, sc.KZGAggregatedProof)
+		}
+	}
+	oks, verr := VerifyAggregateKZGProofBatch(blobs, comms, proofs)
+	for i, j := range rows {
+		if verr[i] != nil {
+			errs[j] = fmt.Errorf("verify_aggregate_kzg_proof error: %v", verr[i])
+		} else if !oks[i] {
+			errs[j] = errInvalidKZGProof
+		}
+	}
+	return errs
 }

@@ -267,6 +267,19 @@ int kzg_hip_eth_set_setup_g2(kzg_hip_eth *eth, const void *setup_g2, uint64_t n)
  * 2 z or y not below r ("invalid evaluation point" / "invalid expected output"), 3 commitment or proof not a valid G1 encoding */
 int kzg_hip_eth_verify_kzg_proof_batch(kzg_hip_eth *eth, const void *commitments48, const void *zs_le32, const void *ys_le32, const void *proofs48, uint64_t count,
                                        uint8_t *result);
+/* eth.VerifyAggregateKZGProof (eth/eth.go:155-172) over `sidecars` blocks.  blob_counts[j] blobs belong to block j (0 is valid); blobs_le32 holds
+ * all blobs in block order (sum(blob_counts) x n x 32 little-endian bytes), commitments48 the expected commitments in the same order, proofs48 one
+ * aggregated proof per block.  result[j]: 1 valid, 0 the pairing check failed, 2 a field element of one of the block's blobs is >= r ("could not
+ * convert blobs to polynomials"), 3 a commitment or the proof of the block is not a valid G1 encoding.  2 wins over 3 (the reference's order).
+ * A row with result 2 or 3 affects no other row.  Optional outputs per block (null to skip; unspecified for rows with result 2 or 3): the
+ * aggregated commitment as 48 compressed bytes, the evaluation challenge z and y = aggregatedPoly(z) as Fr.
+ * Needs kzg_hip_eth_set_setup_g2 (else KZG_HIP_ERR_BAD_ARG); sidecars == 0 is KZG_HIP_OK; KZG_HIP_ERR_TOO_WIDE when the sum of blob_counts
+ * overflows.  The blobs are uploaded once per chunk of whole sidecars (KZG_HIP_ETH_VERIFY_CHUNK_MB of blob bytes, default 4096) and everything runs
+ * on the device: the Fiat-Shamir transcripts (one lane per sidecar; KZG_HIP_ETH_TRANSCRIPT=host|device forces where they are hashed, the default
+ * goes by the sidecar count), the aggregated polynomials and commitments, y and the pairing checks.  No commitment table is built. */
+int kzg_hip_eth_verify_aggregate_kzg_proof_batch(kzg_hip_eth *eth, const void *blobs_le32, const uint64_t *blob_counts, const void *commitments48,
+                                                 const void *proofs48, uint64_t sidecars, uint8_t *result,
+                                                 void *out_agg_commitments48, void *out_zs_fr, void *out_ys_fr);
 /* ---- erasure recovery ----
  * FFTSettings.ZeroPolyViaMultiplication (zero_poly.go:116-217): vanishing polynomial of the missing indices of a size-`length`
  * domain; writes `length` evaluations and `length` coefficients (zero-padded).  No missing index -> all zeros (:117-119). */

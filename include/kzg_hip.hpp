@@ -335,6 +335,24 @@ class Settings {
         detail::must(kzg_hip_eth_verify_kzg_proof_batch(h_, commitments.data(), zs.data(), ys.data(), proofs.data(), out.size(), out.data()));
         return out;
     }
+    // eth.VerifyAggregateKZGProof over many sidecars (eth/eth.go:155-172): 1 valid, 0 pairing check failed, 2 a field element >= r, 3 undecodable
+    // commitment / proof.  blobs[j] / commitments[j]: the blobs and the expected commitments of block j (none is valid)
+    std::vector<uint8_t> VerifyAggregateKZGProofBatch(const std::vector<std::vector<Blob>> &blobs, const std::vector<std::vector<Bytes48>> &commitments,
+                                                      const std::vector<Bytes48> &proofs) const {
+        std::vector<uint8_t> out(blobs.size()), flat;
+        std::vector<uint64_t> counts(blobs.size());
+        std::vector<Bytes48> comm;
+        if (commitments.size() != out.size() || proofs.size() != out.size()) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "slice lengths");
+        for (size_t j = 0; j < blobs.size(); j++) {
+            if (commitments[j].size() != blobs[j].size()) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "one commitment per blob");
+            counts[j] = blobs[j].size();
+            for (const auto &b : blobs[j]) { if (b.size() != n_ * 32) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "blob size"); flat.insert(flat.end(), b.begin(), b.end()); }
+            comm.insert(comm.end(), commitments[j].begin(), commitments[j].end());
+        }
+        detail::must(kzg_hip_eth_verify_aggregate_kzg_proof_batch(h_, flat.data(), counts.data(), comm.data(), proofs.data(), out.size(), out.data(), nullptr, nullptr,
+                                                                  nullptr));
+        return out;
+    }
     Fr EvaluatePolynomialInEvaluationForm(const std::vector<Fr> &poly, const Fr &x) const {       // eth/helpers.go:207-211
         Fr y; detail::must(kzg_hip_eth_evaluate_polynomial_in_evaluation_form(h_, poly.data(), poly.size(), &x, &y)); return y;
     }
