@@ -211,9 +211,32 @@ template <class F> KZG_HD felem<F> mont_mul_inl(const felem<F> &a, const felem<F
 // so in a saturated 32-bit CIOS the carry handling costs as much as the 288 multiplies themselves.  With 13 limbs of
 // 30 bits every partial product (< 2^60) is accumulated by ONE v_mad_u64_u32 into a 64-bit column and columns never
 // carry into each other inside a round: 338 mads + ~130 cheap ops instead of 288 mads + ~900 carry/move ops.
-// A column holds at most 14 products between sweeps (14 * 2^60 < 2^64): one carry sweep after round 7 keeps it exact.
+// A column holds at most 14 products between sweeps (14 * 2^60 + 2^35 < 2^64): one carry sweep after round 7 keeps it exact.
 // Inputs and output are canonical (< p) in 12 x u32 storage.
 // ---------------------------------------------------------------------------------------------
+// carry sweep over columns [0, n): only the HIGH WORD of a column has to move for the column to stay below 2^64, so column j + 1 takes 4 * hi(column j) by one
+// multiply-add and column j keeps its low 32 bits (a move of zero into the high word) -- 2 instructions per column where shift, 64-bit add, mask and move
+// were 4.  The total sum(col[j] 2^(30 j)) is unchanged: 2^32 hi 2^(30 j) = 4 hi 2^(30 (j + 1)).  The sweep RIPPLES upwards: column j + 1 takes its carry before
+// its own high word is read, so both steps work in place on the column's register pair (a form that reads every high word first has independent multiply-adds
+// but cost 169 register copies per mixed addition).  Afterwards col[j] < 2^32 for j < n - 1 and col[n - 1] keeps its high word; the cores below quote the
+// looser 2^35, which is all their bounds need.
+// The factor 4 is made opaque to the device compiler (an empty asm on a scalar register): a visible constant is strength-reduced to a shift, which needs the high
+// word widened to a register pair and costs two moves more than the multiply-add.
+KZG_HD uint32_t sweep_factor() {
+    uint32_t four = 4u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(four));
+#endif
+    return four;
+}
+template <int n> KZG_HD void sweep_hi(uint64_t *col) {
+    const uint32_t four = sweep_factor();
+#pragma unroll
+    for (int j = 0; j + 1 < n; j++) {
+        col[j + 1] += (uint64_t)(uint32_t)(col[j] >> 32) * four;
+        col[j] = (uint32_t)col[j];
+    }
+}
 KZG_HD void unpack30(uint32_t *o, const fp &a) {
 #pragma unroll
     for (int k = 0; k < 13; k++) {
@@ -239,10 +262,7 @@ KZG_HD void mont_core30(uint32_t *r, const uint32_t *A, const uint32_t *B) {
 #pragma unroll
         for (int j = 0; j < 13; j++) acc[j] = acc[j + 1];
         acc[13] = 0;
-        if (i == 6) {                                 // carry sweep: keeps every column below 2^64
-#pragma unroll
-            for (int j = 0; j < 12; j++) { acc[j + 1] += acc[j] >> 30; acc[j] &= 0x3fffffffull; }
-        }
+        if (i == 6) sweep_hi<13>(acc);                // carry sweep: keeps every column below 2^64
     }
     uint64_t c = 0;
 #pragma unroll
@@ -267,17 +287,14 @@ KZG_HD void mont_core30_dot2(uint32_t *r, const uint32_t *A, const uint32_t *B, 
 #pragma unroll
         for (int j = 0; j < 13; j++) acc[j] = acc[j + 1];
         acc[13] = 0;
-        if ((i & 3) == 3) {                           // <= 12 products of 2^60 (+ one swept carry) per column between sweeps
-#pragma unroll
-            for (int j = 0; j < 12; j++) { acc[j + 1] += acc[j] >> 30; acc[j] &= 0x3fffffffull; }
-        }
+        if ((i & 3) == 3) sweep_hi<13>(acc);          // <= 12 products of 2^60 (+ a swept rest below 2^35) per column between sweeps
     }
     uint64_t c = 0;
 #pragma unroll
     for (int j = 0; j < 13; j++) { uint64_t x = acc[j] + c; r[j] = (uint32_t)x & 0x3fffffffu; c = x >> 30; }
 }
 // squaring: the 78 cross products are formed once with a doubled operand (2 A[j] < 2^31, product < 2^61; a column holds at
-// most 6 of them + one square: < 2^64), all 26 columns are swept, then the 13 reduction rounds add at most 13 products of
+// most 6 of them + one square: < 2^64), all 26 columns are swept (to below 2^35), then the 13 reduction rounds add at most 13 products of
 // 2^60 per column.  91 + 169 = 260 multiplies instead of 338.
 KZG_HD void mont_sqr_core30(uint32_t *r, const uint32_t *A) {
     uint64_t T[26];
@@ -292,8 +309,7 @@ KZG_HD void mont_sqr_core30(uint32_t *r, const uint32_t *A) {
 #pragma unroll
         for (int j = i + 1; j < 13; j++) T[i + j] += (uint64_t)A2[j] * A[i];
     }
-#pragma unroll
-    for (int c = 0; c < 25; c++) { T[c + 1] += T[c] >> 30; T[c] &= 0x3fffffffull; }
+    sweep_hi<26>(T);
 #pragma unroll
     for (int i = 0; i < 13; i++) {
         uint32_t m = ((uint32_t)T[i] * FpP::INV30) & 0x3fffffffu;
@@ -662,7 +678,7 @@ template <class F> KZG_HD felem<F> inv(const felem<F> &x) {
             const int32_t sf0 = sw ? f1 : f0, sf1 = sw ? f0 : f1, sg0 = sw ? g1 : g0, sg1 = sw ? g0 : g1;
             xa = (odd ? sa - sb : sa) >> 1; xb = sb;
             f0 = odd ? sf0 - sf1 : sf0; g0 = odd ? sg0 - sg1 : sg0;
-            f1 = sf1 << 1; g1 = sg1 << 1;
+            f1 = (int32_t)((uint32_t)sf1 << 1); g1 = (int32_t)((uint32_t)sg1 << 1);   // (doubling a negative factor: shifted as unsigned, a signed shift of it is undefined before C++20)
         }
         // (a, b) <- (f0 a + g0 b, f1 a + g1 b) / 2^30, exact division; a negative row is negated (with its factors)
         int64_t ca = 0, cb = 0;
