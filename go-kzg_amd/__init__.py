@@ -94,6 +94,10 @@ def lib():
         "kzg_hip_compute_proof_multi": (i32, [vp, vp, u64, u64, u64, vp]),
         "kzg_hip_check_proof_multi_interpolation": (i32, [vp, vp, u64, vp, vp, vp]),
         "kzg_hip_g2_from_compressed": (i32, [vp, vp, u64, vp]), "kzg_hip_pairings_verify_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
+        "kzg_hip_g2_mul_generator_vec": (i32, [vp, vp, u64, vp]), "kzg_hip_generate_testing_setup_g2": (i32, [vp, vp, u64, vp]),
+        "kzg_hip_g2_to_compressed": (i32, [vp, vp, u64, vp]),
+        "kzg_hip_trusted_setup_g2_from_json": (i32, [vp, C.c_char_p, u64, vp, u64, C.POINTER(u64)]),
+        "kzg_hip_test_g2_table_builds": (i32, [vp, C.POINTER(u64)]),
         "kzg_hip_kzg_set_secret_g2": (i32, [vp, vp, u64]), "kzg_hip_check_proof_single_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "kzg_hip_check_proof_multi_batch": (i32, [vp, vp, vp, vp, vp, u64, u64, vp]),
         "kzg_hip_eth_set_setup_g2": (i32, [vp, vp, u64]), "kzg_hip_eth_verify_kzg_proof_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
@@ -426,7 +430,7 @@ class FFTSettings:
         return out
 
     def trusted_setup_from_json(self, text):
-        """JSONTrustedSetup (eth/globals.go:33-49): JSON text -> (setup_G1, setup_G1_lagrange) as Kilic images; G2 is skipped"""
+        """JSONTrustedSetup (eth/globals.go:33-49): JSON text -> (setup_G1, setup_G1_lagrange) as Kilic images; trusted_setup_g2_from_json reads setup_G2"""
         raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
         n1, n2 = C.c_uint64(0), C.c_uint64(0)
         _chk(lib().kzg_hip_trusted_setup_from_json(self.h, raw, len(raw), None, None, 0, C.byref(n1), C.byref(n2)))
@@ -447,6 +451,64 @@ class FFTSettings:
         out = g1_empty(n)
         _chk(lib().kzg_hip_generate_testing_setup_g1(self.h, _p(secret_fr), n, _p(out)))
         return out
+
+
+    def mul_gen_g2_vec(self, scalars):
+        """bls.MulG2(&out[i], &bls.GenG2, &scalars[i]) over a slice -> (n, 3, 2, 6) Kilic G2 images with Z = 1 (infinity: (0, 1, 0))"""
+        scalars = _fr(scalars)
+        out = g2_empty(scalars.shape[0])
+        _chk(lib().kzg_hip_g2_mul_generator_vec(self.h, _p(scalars), scalars.shape[0], _p(out)))
+        return out
+
+    def generate_testing_setup_g2(self, secret_fr, n):
+        """GenerateTestingSetup (setup.go:9-26), G2 half: out[i] = [secret^i] G2; secret_fr is the Montgomery image of the secret"""
+        secret_fr = _fr(secret_fr)
+        out = g2_empty(n)
+        _chk(lib().kzg_hip_generate_testing_setup_g2(self.h, _p(secret_fr), n, _p(out)))
+        return out
+
+    def to_compressed_g2(self, points):
+        """bls.ToCompressedG2 over a slice (bls/bls_kilic.go:123-125): (n, 3, 2, 6) images, any Z -> (n, 96) uint8"""
+        points = _g2(points)
+        out = np.zeros((points.shape[0], 96), dtype=np.uint8)
+        _chk(lib().kzg_hip_g2_to_compressed(self.h, _p(points), points.shape[0], _p(out)))
+        return out
+
+    def g2_marshal_text(self, points):
+        """bls.G2Point.MarshalText over a slice (bls/bls_all.go:41-43): lower-case hex of the 96-byte compressed form"""
+        return [bytes(row).hex() for row in self.to_compressed_g2(points)]
+
+    def g2_unmarshal_text(self, texts):
+        """bls.G2Point.UnmarshalText over a slice (bls/bls_all.go:45-60): hex decoding here, decompression and subgroup check on the device"""
+        texts = list(texts)
+        try:
+            raw = [bytes.fromhex(t) for t in texts]
+        except ValueError:
+            raise KzgPanic(ERR_BAD_POINT, "invalid hex in a G2 point") from None
+        if any(len(r) != 96 for r in raw):
+            raise KzgPanic(ERR_BAD_POINT, "expected 96-byte compressed G2 points")
+        return self.g2_from_compressed(np.frombuffer(b"".join(raw), dtype=np.uint8).reshape(-1, 96))
+
+    def trusted_setup_g2_from_json(self, text):
+        """the "setup_G2" array of a JSONTrustedSetup document (eth/globals.go:35,47) as Kilic G2 images; none when the key is absent"""
+        raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        n = C.c_uint64(0)
+        _chk(lib().kzg_hip_trusted_setup_g2_from_json(self.h, raw, len(raw), None, 0, C.byref(n)))
+        out = g2_empty(n.value)
+        if n.value:
+            _chk(lib().kzg_hip_trusted_setup_g2_from_json(self.h, raw, len(raw), _p(out), n.value, C.byref(n)))
+        return out[:n.value]
+
+    def g2_table_builds(self):
+        """test hook: how many times this handle built its fixed-base table of bls.GenG2"""
+        n = C.c_uint64(0)
+        _chk(lib().kzg_hip_test_g2_table_builds(self.h, C.byref(n)))
+        return n.value
+
+
+def generate_testing_setup(fs, secret_fr, n):
+    """GenerateTestingSetup (setup.go:9-26): ([secret^i] G1, [secret^i] G2) for i < n, both halves on the device"""
+    return fs.generate_testing_setup_g1(secret_fr, n), fs.generate_testing_setup_g2(secret_fr, n)
 
 
 class G1Points:
@@ -488,13 +550,23 @@ def commit_to_eval_poly(fs, secret_g1_ifft, eval_poly):
 
 
 class KZGSettings:
-    """kzg.KZGSettings, prover side (kzg.go:11-36): SecretG1 is uploaded once and stays in HBM."""
+    """kzg.KZGSettings (kzg.go:11-36): SecretG1 is uploaded once and stays in HBM; with secret_g2 the object also verifies (set_secret_g2)."""
 
-    def __init__(self, fs, secret_g1):
+    def __init__(self, fs, secret_g1, secret_g2=None):
         secret_g1 = _g1(secret_g1)
+        if secret_g2 is not None:
+            secret_g2 = _g2(secret_g2)
+            if secret_g2.shape[0] != secret_g1.shape[0]:
+                raise KzgPanic(ERR_LEN_MISMATCH, "secret list lengths don't match")   # kzg.go:22-27
         h = C.c_void_p()
         _chk(lib().kzg_hip_kzg_settings_new(fs.h, _p(secret_g1), secret_g1.shape[0], C.byref(h)))
         self.h, self.fs, self.n_setup = h, fs, secret_g1.shape[0]
+        if secret_g2 is not None:
+            try:
+                self.set_secret_g2(secret_g2)
+            except KzgError:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None):

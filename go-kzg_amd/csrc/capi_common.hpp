@@ -73,6 +73,7 @@ struct kzg_hip_fft {
     std::mutex mu;
     struct pool_slot { hipStream_t s = nullptr; uint8_t *h_pin = nullptr; size_t pin_cap = 0; };   // a stream + its pinned staging area (stream_lease)
     std::mutex pool_mu; std::condition_variable pool_cv; std::vector<pool_slot> pool_idle; int pool_total = 0;
+    g2a *d_g2_fb = nullptr; uint64_t g2_fb_builds = 0;   // fixed-base table of bls.GenG2 (g2.hpp: G2_FB_ENTRIES affine entries, 1.5 MiB), built under `mu` by the first call that multiplies the generator (capi_verify.hip)
     struct lincomb_promo *promo = nullptr;   // kzg_hip_lincomb_g1's memory of recent caller-supplied point sets (capi_core.hip); created on first use
 };
 struct g2_state;   // capi_verify.hip: the G2 points a handle verifies against

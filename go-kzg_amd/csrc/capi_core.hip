@@ -174,7 +174,7 @@ void kzg_hip_fft_settings_free(kzg_hip_fft *fs) {
     hipSetDevice(fs->device);
     lincomb_promo_free(fs);                                 // promoted point sets hold tables and coalescers on this handle: they go first
     if (fs->stream) hipStreamSynchronize(fs->stream);
-    hipFree(fs->d_expanded); hipFree(fs->d_reversed); hipFree(fs->d_expanded_l); hipFree(fs->d_reversed_l); hipFree(fs->d_inv_pow2); hipFree(fs->d_tw4096[0]); hipFree(fs->d_tw4096[1]); hipFree(fs->d_tw_das2048); hipFree(fs->d_glv_expanded); hipFree(fs->d_glv_reversed); hipFree(fs->d_wnaf_expanded); hipFree(fs->d_wnaf_reversed);
+    hipFree(fs->d_expanded); hipFree(fs->d_reversed); hipFree(fs->d_expanded_l); hipFree(fs->d_reversed_l); hipFree(fs->d_inv_pow2); hipFree(fs->d_tw4096[0]); hipFree(fs->d_tw4096[1]); hipFree(fs->d_tw_das2048); hipFree(fs->d_glv_expanded); hipFree(fs->d_glv_reversed); hipFree(fs->d_wnaf_expanded); hipFree(fs->d_wnaf_reversed); hipFree(fs->d_g2_fb);
     if (fs->stream) { stream_cache_disown(fs->stream); hipStreamDestroy(fs->stream); }
     if (fs->h_stage) hipHostFree(fs->h_stage);
     for (auto &ps : fs->pool_idle) { hipStreamSynchronize(ps.s); stream_cache_disown(ps.s); hipStreamDestroy(ps.s); if (ps.h_pin) hipHostFree(ps.h_pin); }

@@ -457,8 +457,8 @@ int kzg_hip_g1_unmarshal_text(kzg_hip_fft *fs, const char *hex96, uint64_t n, vo
     return kzg_hip_g1_from_compressed(fs, raw.data(), n, out_g1);
     KZG_CATCH
 }
-// finds "key" : [ "..." , ... ] in `js` and appends the decoded 48-byte strings; *found = 0 when the key is absent
-static int json_hex48_array(const char *js, uint64_t len, const char *key, std::vector<uint8_t> &out, uint64_t *count, int *found) {
+// finds "key" : [ "..." , ... ] in `js` and appends the decoded strings of `width` bytes each (48: G1, 96: G2); *found = 0 when the key is absent
+static int json_hex_array(const char *js, uint64_t len, const char *key, int width, std::vector<uint8_t> &out, uint64_t *count, int *found) {
     *count = 0; *found = 0;
     std::string pat = std::string("\"") + key + "\"";
     const char *end = js + len, *p = js;
@@ -483,8 +483,8 @@ static int json_hex48_array(const char *js, uint64_t len, const char *key, std::
         const char *q = p;
         while (q < end && *q != '"') q++;
         if (q == end) return KZG_HIP_ERR_BAD_ARG;
-        if (q - p != 96) return KZG_HIP_ERR_BAD_POINT;                   // FromCompressedG1 wants exactly 48 bytes
-        for (int i = 0; i < 48; i++) {
+        if (q - p != 2 * width) return KZG_HIP_ERR_BAD_POINT;            // FromCompressedG1 / G2 want exactly 48 / 96 bytes
+        for (int i = 0; i < width; i++) {
             int hi = hex_nibble(p[2 * i]), lo = hex_nibble(p[2 * i + 1]);
             if (hi < 0 || lo < 0) return KZG_HIP_ERR_BAD_POINT;
             out.push_back((uint8_t)(hi << 4 | lo));
@@ -499,8 +499,8 @@ int kzg_hip_trusted_setup_from_json(kzg_hip_fft *fs, const char *json, uint64_t 
     KZG_TRY
     std::vector<uint8_t> mono, lagr;
     int f1 = 0, f2 = 0;
-    CHK(json_hex48_array(json, json_len, "setup_G1", mono, n_setup_g1, &f1));
-    CHK(json_hex48_array(json, json_len, "setup_G1_lagrange", lagr, n_lagrange_g1, &f2));
+    CHK(json_hex_array(json, json_len, "setup_G1", 48, mono, n_setup_g1, &f1));
+    CHK(json_hex_array(json, json_len, "setup_G1_lagrange", 48, lagr, n_lagrange_g1, &f2));
     if (!f1 && !f2) return KZG_HIP_ERR_BAD_ARG;                          // not a trusted-setup document
     if (out_setup_g1 && *n_setup_g1) {
         if (*n_setup_g1 > capacity) return KZG_HIP_ERR_LEN_MISMATCH;
@@ -509,6 +509,21 @@ int kzg_hip_trusted_setup_from_json(kzg_hip_fft *fs, const char *json, uint64_t 
     if (out_lagrange_g1 && *n_lagrange_g1) {
         if (*n_lagrange_g1 > capacity) return KZG_HIP_ERR_LEN_MISMATCH;
         CHK(kzg_hip_g1_from_compressed(fs, lagr.data(), *n_lagrange_g1, out_lagrange_g1));
+    }
+    return KZG_HIP_OK;
+    KZG_CATCH
+}
+// the "setup_G2" array of the same document (eth/globals.go:35,47): bls.FromCompressedG2 of every entry on the device.  Same two-call protocol;
+// a document without the key has no G2 points (count 0)
+int kzg_hip_trusted_setup_g2_from_json(kzg_hip_fft *fs, const char *json, uint64_t json_len, void *out_setup_g2, uint64_t capacity, uint64_t *n_setup_g2) {
+    if (!fs || !json || !n_setup_g2) return KZG_HIP_ERR_BAD_ARG;
+    KZG_TRY
+    std::vector<uint8_t> raw;
+    int found = 0;
+    CHK(json_hex_array(json, json_len, "setup_G2", 96, raw, n_setup_g2, &found));
+    if (out_setup_g2 && *n_setup_g2) {
+        if (*n_setup_g2 > capacity) return KZG_HIP_ERR_LEN_MISMATCH;
+        CHK(kzg_hip_g2_from_compressed(fs, raw.data(), *n_setup_g2, out_setup_g2));
     }
     return KZG_HIP_OK;
     KZG_CATCH

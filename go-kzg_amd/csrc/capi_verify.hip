@@ -86,6 +86,39 @@ int run_shared_check(hipStream_t s, const g2_prepared *gen, const g2_prepared *q
     HIPCHK(hipStreamSynchronize(s));
     return KZG_HIP_OK;
 }
+// the handle's fixed-base table of bls.GenG2, built once on the handle's stream; the caller holds fs->mu (dev_guard)
+int ensure_g2_table(kzg_hip_fft *fs) {
+    if (fs->d_g2_fb) return KZG_HIP_OK;
+    g2a *t = nullptr;
+    HIPCHK(hipMalloc((void **)&t, G2_FB_ENTRIES * sizeof(g2a)));
+    launch_g2_fixed_base_table(fs->stream, t);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(fs->stream);
+    if (e != hipSuccess) { (void)hipFree(t); HIPCHK(e); }
+    fs->d_g2_fb = t; fs->g2_fb_builds++;
+    return KZG_HIP_OK;
+}
+// out[i] = [k_i] G2 as normalised Kilic images, k = the n scalars at scalars_fr, or the powers secret^0 .. secret^(n - 1) when powers_of_one
+int g2_mul_generator(kzg_hip_fft *fs, const void *scalars_fr, bool powers_of_one, uint64_t n, void *out_g2) {
+    dev_guard g(fs);
+    hipStream_t s = fs->stream;
+    CHK(ensure_g2_table(fs));
+    dtmp<g2j> d_a(s), d_b(s); dtmp<fr> d_k(s), d_s(s);
+    CHK(d_a.alloc(n)); CHK(d_b.alloc(n)); CHK(d_k.alloc(n));
+    if (powers_of_one) {
+        CHK(d_s.alloc(1));
+        HIPCHK(hipMemcpyAsync(d_s.p, scalars_fr, sizeof(fr), hipMemcpyHostToDevice, s));
+        launch_fr_powers(s, d_s.p, n, d_k.p);
+    } else {
+        HIPCHK(hipMemcpyAsync(d_k.p, scalars_fr, n * sizeof(fr), hipMemcpyHostToDevice, s));
+    }
+    launch_g2_fixed_base(s, d_k.p, n, fs->d_g2_fb, d_a.p);
+    launch_g2_normalize(s, d_a.p, n, d_b.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_g2, d_b.p, n * sizeof(g2j), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return KZG_HIP_OK;
+}
 // C - E + [b] pi, -pi for `count` KZG checks (E = [y]G1 from ys, or the points es) and the check against [1]G2, Q1
 // single proofs: ys_fr and xs (bs_fr) are host buffers; multi proofs (ys_fr == null): d_es / d_bs are DEVICE buffers on stream s
 int kzg_checks(hipStream_t s, const g2_prepared *gen, const g2_prepared *q1, const void *c_g1, const void *pi_g1, const void *ys_fr, const g1j *d_es,
@@ -126,6 +159,44 @@ int kzg_hip_g2_from_compressed(kzg_hip_fft *fs, const void *in96, uint64_t n, vo
     HIPCHK(hipStreamSynchronize(s));
     return bad ? KZG_HIP_ERR_BAD_POINT : KZG_HIP_OK;
     KZG_CATCH
+}
+
+int kzg_hip_g2_mul_generator_vec(kzg_hip_fft *fs, const void *scalars_fr, uint64_t n, void *out_g2) {
+    if (!fs || (n && (!scalars_fr || !out_g2))) return KZG_HIP_ERR_BAD_ARG;
+    if (!n) return KZG_HIP_OK;
+    KZG_TRY
+    return g2_mul_generator(fs, scalars_fr, false, n, out_g2);
+    KZG_CATCH
+}
+int kzg_hip_generate_testing_setup_g2(kzg_hip_fft *fs, const void *secret_fr, uint64_t n, void *out_g2) {
+    if (!fs || !secret_fr || (n && !out_g2)) return KZG_HIP_ERR_BAD_ARG;
+    if (!n) return KZG_HIP_OK;
+    KZG_TRY
+    return g2_mul_generator(fs, secret_fr, true, n, out_g2);
+    KZG_CATCH
+}
+int kzg_hip_g2_to_compressed(kzg_hip_fft *fs, const void *points_g2, uint64_t n, void *out96) {
+    if (!fs || (n && (!points_g2 || !out96))) return KZG_HIP_ERR_BAD_ARG;
+    if (!n) return KZG_HIP_OK;
+    KZG_TRY
+    stream_lease lease(fs);
+    hipStream_t s = lease.s;
+    dtmp<g2j> d_in(s); dtmp<uint8_t> d_out(s);
+    CHK(d_in.alloc(n)); CHK(d_out.alloc(96 * n));
+    HIPCHK(hipMemcpyAsync(d_in.p, points_g2, n * sizeof(g2j), hipMemcpyHostToDevice, s));
+    launch_g2_compress(s, d_in.p, n, d_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out96, d_out.p, 96 * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return KZG_HIP_OK;
+    KZG_CATCH
+}
+// test hook (kzg_hip_internal.h): how many times this handle built its table of bls.GenG2 (0 before the first use, then 1)
+int kzg_hip_test_g2_table_builds(kzg_hip_fft *fs, uint64_t *builds) {
+    if (!fs || !builds) return KZG_HIP_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(fs->mu);
+    *builds = fs->g2_fb_builds;
+    return KZG_HIP_OK;
 }
 
 int kzg_hip_pairings_verify_batch(kzg_hip_fft *fs, const void *a1_g1, const void *a2_g2, const void *b1_g1, const void *b2_g2, uint64_t n, uint8_t *ok) {

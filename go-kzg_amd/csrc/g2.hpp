@@ -64,6 +64,30 @@ KZG_TW g2j g2_add(const g2j &p, const g2j &q) {
     o.z = fp2_mul(fp2_sub(fp2_sub(fp2_sqr(fp2_add(p.z, q.z)), z1z1), z2z2), h);
     return o;
 }
+// An affine "no point": (0, 0) is not on the twist (b != 0) and is what g2_to_affine returns for infinity; a table entry of that form adds nothing
+KZG_HD bool g2a_is_none(const g2a &q) { return fp2_is_zero(q.x) && fp2_is_zero(q.y); }
+// madd-2007-bl over F_p2 (Jacobian + affine: 7 products and 4 squarings against the 11 + 5 of g2_add), exceptional cases handled as in g2_add:
+// Q "no point" returns P, P at infinity returns Q, P == Q doubles, P == -Q gives infinity
+KZG_TW g2j g2_add_mixed(const g2j &p, const g2a &q) {
+    if (g2a_is_none(q)) return p;
+    if (is_inf(p)) { g2j o; o.x = q.x; o.y = q.y; o.z = fp2_one(); return o; }
+    fp2 z1z1 = fp2_sqr(p.z);
+    fp2 u2 = fp2_mul(q.x, z1z1), s2 = fp2_mul(fp2_mul(q.y, p.z), z1z1);
+    if (fp2_equal(u2, p.x)) {
+        if (fp2_equal(s2, p.y)) return g2_dbl(p);
+        return g2_inf();
+    }
+    fp2 h = fp2_sub(u2, p.x), hh = fp2_sqr(h);
+    fp2 i = fp2_dbl(fp2_dbl(hh));
+    fp2 j = fp2_mul(h, i);
+    fp2 r = fp2_dbl(fp2_sub(s2, p.y));
+    fp2 v = fp2_mul(p.x, i);
+    g2j o;
+    o.x = fp2_sub(fp2_sub(fp2_sub(fp2_sqr(r), j), v), v);
+    o.y = fp2_sub(fp2_mul(r, fp2_sub(v, o.x)), fp2_dbl(fp2_mul(p.y, j)));
+    o.z = fp2_sub(fp2_sub(fp2_sqr(fp2_add(p.z, h)), z1z1), hh);
+    return o;
+}
 // k P for a standard-form scalar of `words` u32 limbs, MSB first, bitwise (setup and subgroup checks only)
 KZG_HD g2j g2_mul_bits(const g2j &p, const uint32_t *k, int words) {
     g2j acc = g2_inf();
@@ -158,6 +182,63 @@ KZG_HD bool g2_decompress(g2j &out, const uint8_t *b) {
     if (!g2_in_subgroup(p)) return false;
     out = p;
     return true;
+}
+
+// bls.ToCompressedG2 (Kilic G2.ToCompressed), the exact inverse of g2_decompress: x.c1 || x.c0 big-endian, 0x80 set, 0x20 from fp2_lex_larger(y),
+// c0 00 .. 00 for infinity.  Device-internal image in, any Z (one F_p inversion when Z != 1).
+KZG_HD void fp_to_be48(uint8_t *o, const fp &std) {
+    for (int i = 0; i < 48; i++) o[47 - i] = (uint8_t)(std.l[i >> 2] >> (8 * (i & 3)));
+}
+KZG_HD void g2_compress(uint8_t *o, const g2j &p) {
+    if (is_inf(p)) {
+        o[0] = 0xc0;
+        for (int i = 1; i < 96; i++) o[i] = 0;
+        return;
+    }
+    g2a a;
+    if (fp2_equal(p.z, fp2_one())) { a.x = p.x; a.y = p.y; }
+    else a = g2_to_affine(p);
+    fp_to_be48(o, from_mont<FpP>(a.x.c1));
+    fp_to_be48(o + 48, from_mont<FpP>(a.x.c0));
+    o[0] |= 0x80 | (fp2_lex_larger(a.y) ? 0x20 : 0);
+}
+// the API's output form of a G2 result: Kilic image with Z = 1, infinity as Kilic's Zero() (0, 1, 0); one F_p inversion
+KZG_HD g2j g2_normalize_to_kilic(const g2j &p) {
+    if (is_inf(p)) return g2_to_kilic(g2_inf());
+    const g2a a = g2_to_affine(p);
+    g2j o; o.x = a.x; o.y = a.y; o.z = fp2_one();
+    return g2_to_kilic(o);
+}
+
+// ---------------- fixed-base multiplication of bls.GenG2 ----------------
+// T[w][d] = [d 2^(8 w)] G2 for w = 0..31, d = 0..255, affine, device-internal Montgomery domain; T[w][0] is the "no point" entry.  UNSIGNED 8-bit
+// windows: a digit is a byte of the standard-form scalar, a row is indexed by it without a branch or a negation, and 32 x 256 x 192 B = 1.5 MiB
+// stays resident in the L2.  A multiplication is 32 mixed additions and no doubling (g2_mul_bits: 255 doublings and ~127 full additions).
+constexpr int G2_FB_C = 8, G2_FB_WINDOWS = 32, G2_FB_ROW = 1 << G2_FB_C;
+constexpr uint64_t G2_FB_ENTRIES = (uint64_t)G2_FB_WINDOWS * G2_FB_ROW;
+KZG_HD uint32_t g2_fb_digit(const fr &k_std, int w) { return (k_std.l[w >> 2] >> (8 * (w & 3))) & 0xffu; }   // digit w of a STANDARD-form scalar
+KZG_HD g2j g2_fb_window_base(int w) {   // [2^(8 w)] G2
+    g2j b = g2_generator();
+    for (int i = 0; i < G2_FB_C * w; i++) b = g2_dbl(b);
+    return b;
+}
+KZG_HD g2a g2_fb_entry(const g2j &base, uint32_t d) {   // [d] base, d < 256; d == 0: "no point"
+    g2j acc = g2_inf();
+    for (int i = G2_FB_C - 1; i >= 0; i--) {
+        acc = g2_dbl(acc);
+        if ((d >> i) & 1u) acc = g2_add(acc, base);
+    }
+    return g2_to_affine(acc);
+}
+// [k] G2 for a Montgomery-form scalar k < r: the scalar leaves the Montgomery domain once and is cut into bytes.  No partial sum meets an
+// exceptional case of the addition: after windows 0 .. w - 1 the sum is [k mod 2^(8 w)] G2, a multiple below 2^(8 w), and the next entry is
+// [d 2^(8 w)] G2 with d >= 1, a larger multiple, so the two differ; their sum is [k mod 2^(8 w + 8)] G2 with 0 < k mod 2^(8 w + 8) <= k < r, so
+// they are not opposite either.  (Only the first non-zero digit meets the accumulator at infinity.)  The complete addition is called anyway.
+KZG_HD g2j g2_fb_mul(const g2a *table, const fr &k_mont) {
+    const fr k = from_mont<FrP>(k_mont);
+    g2j acc = g2_inf();
+    for (int w = 0; w < G2_FB_WINDOWS; w++) acc = g2_add_mixed(acc, table[(uint64_t)w * G2_FB_ROW + g2_fb_digit(k, w)]);
+    return acc;
 }
 
 // ---------------- Miller-loop steps ----------------

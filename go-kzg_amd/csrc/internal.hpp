@@ -151,6 +151,15 @@ void launch_eth_check_inputs(hipStream_t s, const uint8_t *c48, const uint8_t *z
 void launch_pairing_check(hipStream_t s, bool shared_lines, const g2_prepared *q0, const g2_prepared *q1, const g1j *p0, const g1j *p1, uint64_t n, uint8_t *ok);
 void launch_pairing_value(hipStream_t s, const g1j *g1_kilic, const g2_prepared *q, uint64_t n, fp *out);   // test hook: reduced e(g1[i], Q_i), standard form
 
+// ---------------- k_g2.hip ----------------
+// the G2 half of a setup (g2.hpp): the fixed-base table of bls.GenG2 (G2_FB_ENTRIES affine entries, device-internal domain), the walk over it
+// (Montgomery scalars in, device-internal Jacobian images out), the API's output form (Kilic images, Z = 1, infinity (0, 1, 0)) and compression
+struct g2a;
+void launch_g2_fixed_base_table(hipStream_t s, g2a *table);
+void launch_g2_fixed_base(hipStream_t s, const fr *scalars, uint64_t n, const g2a *table, g2j *out);
+void launch_g2_normalize(hipStream_t s, const g2j *in, uint64_t n, g2j *out_kilic);
+void launch_g2_compress(hipStream_t s, const g2j *in_kilic, uint64_t n, uint8_t *out96);
+
 // ---------------- k_eth_aggregate.hip ----------------
 // eth.VerifyAggregateKZGProof over a chunk of sidecars: off[j] .. off[j + 1] (sidecars + 1 entries) are sidecar j's blobs and commitments
 // within the chunk's raw bytes (blobs: n x 32 little-endian bytes each; comms: 48 bytes each).  Challenges and powers are Montgomery images.

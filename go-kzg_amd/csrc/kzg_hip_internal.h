@@ -57,6 +57,10 @@ int kzg_hip_test_hash_to_bls_field_lanes(kzg_hip_fft *fs, const void *digests32,
  * exponentiation), 12 F_p elements of 48 bytes each in STANDARD form, order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1; G1 / G2 Kilic images in */
 int kzg_hip_pairing_test(kzg_hip_fft *fs, const void *g1, const void *g2, uint64_t n, void *out_fp12);
 
+/* test hook of the G2 half of a setup (capi_verify.hip): how many times the handle built its fixed-base table of bls.GenG2 -- 0 before the first
+ * kzg_hip_g2_mul_generator_vec / kzg_hip_generate_testing_setup_g2, 1 ever after, however many threads made the first call at once */
+int kzg_hip_test_g2_table_builds(kzg_hip_fft *fs, uint64_t *builds);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 //go:build kzg_hip && !bignum_pure && !bignum_hol256 && !bignum_hbls
 // +build kzg_hip,!bignum_pure,!bignum_hol256,!bignum_hbls
 
-// File for package bls (bls/pairing_hip.go): batch forms of bls.PairingsVerify and bls.FromCompressedG2 on the device.  The lone calls
+// File for package bls (bls/pairing_hip.go): batch forms of bls.PairingsVerify, bls.FromCompressedG2, bls.ToCompressedG2 and
+// bls.MulG2(.., &GenG2, ..) on the device.  The lone calls
 // (PairingsVerify, FromCompressedG2) stay on Kilic: one check is one lane's work (INTEGRATION.md).  G2Point keeps Kilic's memory image,
 // [3][2][6]uint64 Jacobian Montgomery, which is what the C ABI takes.
 package bls
@@ -53,4 +54,30 @@ func FromCompressedG2Batch(in [][96]byte) ([]G2Point, error) {
 		panic("kzg_hip: g2_from_compressed failed")
 	}
 	return out, nil
+}
+
+// ToCompressedG2Batch: ToCompressedG2 over a slice (any Jacobian Z).  G2Point.MarshalText over a slice is hex.EncodeToString of each row.
+func ToCompressedG2Batch(in []G2Point) [][96]byte {
+	out := make([][96]byte, len(in))
+	if len(in) == 0 {
+		return out
+	}
+	st := C.kzg_hip_g2_to_compressed(hipDomain(0), unsafe.Pointer(&in[0]), C.uint64_t(len(in)), unsafe.Pointer(&out[0]))
+	if st != C.KZG_HIP_OK {
+		panic("kzg_hip: g2_to_compressed failed")
+	}
+	return out
+}
+
+// MulGenG2Batch: out[i] = MulG2(&GenG2, &scalars[i]) by a walk over the handle's table of GenG2, normalised (Z = 1).
+func MulGenG2Batch(scalars []Fr) []G2Point {
+	out := make([]G2Point, len(scalars))
+	if len(scalars) == 0 {
+		return out
+	}
+	st := C.kzg_hip_g2_mul_generator_vec(hipDomain(0), unsafe.Pointer(&scalars[0]), C.uint64_t(len(scalars)), unsafe.Pointer(&out[0]))
+	if st != C.KZG_HIP_OK {
+		panic("kzg_hip: g2_mul_generator_vec failed")
+	}
+	return out
 }

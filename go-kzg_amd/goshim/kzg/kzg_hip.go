@@ -121,7 +121,7 @@ func (p *G1Points) LinComb(factors []bls.Fr) *bls.G1Point {
 }
 
 // LoadTrustedSetupJSON decodes the G1 arrays of a trusted-setup document (JSONTrustedSetup, eth/globals.go:33-49: the init() there
-// would call this instead of json.Unmarshal for SetupG1 / SetupLagrange; SetupG2 stays with encoding/json + Kilic).  Hex decoding
+// would call this instead of json.Unmarshal for SetupG1 / SetupLagrange, and LoadTrustedSetupG2JSON for SetupG2).  Hex decoding
 // happens in the library, decompression and the subgroup check on the device.  Panics like init() does on a malformed document.
 func (fs *FFTSettings) LoadTrustedSetupJSON(text []byte) (setupG1, setupLagrange []bls.G1Point) {
 	defer runtime.KeepAlive(fs) // the finalizer must not free the device handle under a running call
@@ -139,6 +139,23 @@ func (fs *FFTSettings) LoadTrustedSetupJSON(text []byte) (setupG1, setupLagrange
 	setupLagrange = make([]bls.G1Point, cap_)
 	hipMust(C.kzg_hip_trusted_setup_from_json(fs.hip(), cs, C.uint64_t(len(text)), g1Ptr(setupG1), g1Ptr(setupLagrange), cap_, &n1, &n2))
 	return setupG1[:n1], setupLagrange[:n2]
+}
+
+// LoadTrustedSetupG2JSON decodes the "setup_G2" array of the same document (eth/globals.go:35,47) on the device; a document without the
+// key gives an empty slice.  Panics like init() does on a malformed document or an invalid point.
+func (fs *FFTSettings) LoadTrustedSetupG2JSON(text []byte) (setupG2 []bls.G2Point) {
+	defer runtime.KeepAlive(fs) // the finalizer must not free the device handle under a running call
+	if len(text) == 0 {
+		panic("kzg_hip: empty trusted setup")
+	}
+	var n C.uint64_t
+	cs := (*C.char)(unsafe.Pointer(&text[0]))
+	hipMust(C.kzg_hip_trusted_setup_g2_from_json(fs.hip(), cs, C.uint64_t(len(text)), nil, 0, &n))
+	setupG2 = make([]bls.G2Point, n)
+	if n > 0 {
+		hipMust(C.kzg_hip_trusted_setup_g2_from_json(fs.hip(), cs, C.uint64_t(len(text)), unsafe.Pointer(&setupG2[0]), n, &n))
+	}
+	return setupG2[:n]
 }
 
 // ToeplitzPart2 replaces fk20_single.go:59-77.

@@ -10,6 +10,7 @@ import "C"
 
 import (
 	"sync"
+	"unsafe"
 
 	"github.com/protolambda/go-kzg/bls"
 )
@@ -26,24 +27,17 @@ func hipContext() *C.kzg_hip_fft {
 	return hipCtx
 }
 
-// GenerateTestingSetup replaces setup.go:9-26 (**for testing purposes only**, as there): the G1 half -- n fixed-base multiplications
-// [secret^i]G1, 65 536 of them for the scale-16 FK20Multi configuration -- runs on the device; the G2 half stays on the CPU backend (this
-// library has no G2 arithmetic), with the reference's own loop.
+// GenerateTestingSetup replaces setup.go:9-26 (**for testing purposes only**, as there).  Both halves run on the device: n fixed-base
+// multiplications [secret^i]G1 and n more [secret^i]G2 -- 65 536 of each for the scale-16 FK20Multi configuration.  The G2 half walks a table of
+// bls.GenG2 that the handle builds on its first use (32 mixed additions per point instead of bls.MulG2's double-and-add).
 func GenerateTestingSetup(secret string, n uint64) ([]bls.G1Point, []bls.G2Point) {
 	var s bls.Fr
 	bls.SetFr(&s, secret)
 	s1Out := make([]bls.G1Point, n, n)
+	s2Out := make([]bls.G2Point, n, n)
 	if n > 0 {
 		hipMust(C.kzg_hip_generate_testing_setup_g1(hipContext(), frPtr([]bls.Fr{s}), C.uint64_t(n), g1Ptr(s1Out)))
-	}
-	var sPow bls.Fr
-	bls.CopyFr(&sPow, &bls.ONE)
-	s2Out := make([]bls.G2Point, n, n)
-	for i := uint64(0); i < n; i++ {
-		bls.MulG2(&s2Out[i], &bls.GenG2, &sPow)
-		var tmp bls.Fr
-		bls.CopyFr(&tmp, &sPow)
-		bls.MulModFr(&sPow, &tmp, &s)
+		hipMust(C.kzg_hip_generate_testing_setup_g2(hipContext(), frPtr([]bls.Fr{s}), C.uint64_t(n), unsafe.Pointer(&s2Out[0])))
 	}
 	return s1Out, s2Out
 }

@@ -130,7 +130,7 @@ int kzg_hip_g1_marshal_text(kzg_hip_fft *fs, const void *points_g1, uint64_t n, 
 int kzg_hip_g1_unmarshal_text(kzg_hip_fft *fs, const char *hex96, uint64_t n, void *out_g1);
 /* JSONTrustedSetup (eth/globals.go:33-49): decodes the "setup_G1" and "setup_G1_lagrange" arrays of a trusted-setup JSON
  * document (the format of eth/trusted_setup.json) into Kilic images, decompressing and subgroup-checking on the device.  Other
- * keys ("setup_G2", "roots_of_unity") are skipped: G2 stays with the CPU backend.  Counts are always written; the arrays only when
+ * keys ("setup_G2", "roots_of_unity") are skipped: kzg_hip_trusted_setup_g2_from_json decodes "setup_G2".  Counts are always written; the arrays only when
  * the out pointer is non-NULL (call once with NULL to size the buffers).  `capacity` = points each out array can hold. */
 int kzg_hip_trusted_setup_from_json(kzg_hip_fft *fs, const char *json, uint64_t json_len, void *out_setup_g1, void *out_lagrange_g1,
                                     uint64_t capacity, uint64_t *n_setup_g1, uint64_t *n_lagrange_g1);
@@ -251,6 +251,20 @@ int kzg_hip_eth_evaluate_polynomial_in_evaluation_form(kzg_hip_eth *eth, const v
  * kzg_hip_g2_from_compressed: bls.FromCompressedG2 over n 96-byte ZCash encodings -> n G2 images; KZG_HIP_ERR_BAD_POINT if ANY is invalid
  * (flags, x >= p, not on the curve, not in the subgroup), like kzg_hip_g1_from_compressed. */
 int kzg_hip_g2_from_compressed(kzg_hip_fft *fs, const void *in96, uint64_t n, void *out_g2);
+/* The G2 half of a setup.  Outputs are G2 images normalised to Z == R, infinity as Kilic's (0, R, 0): the group elements the reference returns
+ * (bls.EqualG2-equal, identical compressed bytes).  The first multiplication on a handle builds a fixed-base table of bls.GenG2 (1.5 MiB, kept
+ * with the handle); a multiplication is then 32 mixed additions.
+ * bls.MulG2(&out[i], &bls.GenG2, &scalars[i]) over a slice (kzg_single_proofs.go:60, kzg_multi_proofs.go:69, eth/helpers.go:57) */
+int kzg_hip_g2_mul_generator_vec(kzg_hip_fft *fs, const void *scalars_fr, uint64_t n, void *out_g2);
+/* GenerateTestingSetup, G2 half (setup.go:17-24): out[i] = [secret^i] G2 */
+int kzg_hip_generate_testing_setup_g2(kzg_hip_fft *fs, const void *secret_fr, uint64_t n, void *out_g2);
+/* bls.ToCompressedG2 over a slice (bls/bls_kilic.go:123-125): n G2 images (any Z) -> n x 96 B ZCash form, the inverse of kzg_hip_g2_from_compressed */
+int kzg_hip_g2_to_compressed(kzg_hip_fft *fs, const void *points_g2, uint64_t n, void *out96);
+/* the "setup_G2" array of a trusted-setup JSON document (eth/globals.go:35,47) as G2 images, decompressed and subgroup-checked on the device.
+ * Protocol of kzg_hip_trusted_setup_from_json: the count is always written, the array only when the out pointer is non-NULL (KZG_HIP_ERR_LEN_MISMATCH
+ * when `capacity` points do not suffice).  KZG_HIP_ERR_BAD_POINT: a non-hex character, an entry that is not 96 bytes, an invalid point.  A
+ * document without the key: count 0. */
+int kzg_hip_trusted_setup_g2_from_json(kzg_hip_fft *fs, const char *json, uint64_t json_len, void *out_setup_g2, uint64_t capacity, uint64_t *n_setup_g2);
 /* bls.PairingsVerify over n checks: ok[i] = (e(a1[i], a2[i]) == e(b1[i], b2[i])); points at infinity contribute 1 (Kilic's AddPair) */
 int kzg_hip_pairings_verify_batch(kzg_hip_fft *fs, const void *a1_g1, const void *a2_g2, const void *b1_g1, const void *b2_g2, uint64_t n, uint8_t *ok);
 /* KZGSettings.SecretG2 (n >= 2 G2 images, copied): [1]G2 and [s]G2 are prepared at once, [s^n]G2 on the first multi check with n values */

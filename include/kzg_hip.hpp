@@ -12,6 +12,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 #include "kzg_hip.h"
 
@@ -145,6 +146,22 @@ class FFTSettings {
         Fr s = SetFr(secretDecimal);
         std::vector<G1Point> out(n);
         detail::must(kzg_hip_generate_testing_setup_g1(h_, &s, n, out.data()));
+        return out;
+    }
+    // setup.go:9-26, G2 half: [s^i] G2 (normalised images; a walk over the handle's table of bls.GenG2)
+    std::vector<G2Point> GenerateTestingSetupG2(const std::string &secretDecimal, uint64_t n) const {
+        Fr s = SetFr(secretDecimal);
+        std::vector<G2Point> out(n);
+        detail::must(kzg_hip_generate_testing_setup_g2(h_, &s, n, out.data()));
+        return out;
+    }
+    // GenerateTestingSetup (setup.go:9-26): both halves
+    std::pair<std::vector<G1Point>, std::vector<G2Point>> GenerateTestingSetup(const std::string &secretDecimal, uint64_t n) const {
+        return {GenerateTestingSetupG1(secretDecimal, n), GenerateTestingSetupG2(secretDecimal, n)};
+    }
+    std::vector<uint8_t> ToCompressedG2(const std::vector<G2Point> &pts) const {                                             // bls.ToCompressedG2 over a slice
+        std::vector<uint8_t> out(96 * pts.size());
+        detail::must(kzg_hip_g2_to_compressed(h_, pts.data(), pts.size(), out.data()));
         return out;
     }
 
