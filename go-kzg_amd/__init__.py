@@ -130,6 +130,9 @@ def lib():
         "kzg_hip_bench_drop_in_eth_proof": (i32, [vp, vp, u64, u64, u32, u32, vp, C.POINTER(C.c_double)]),
         "kzg_hip_zero_poly_via_multiplication": (i32, [vp, vp, u64, u64, vp, vp]),
         "kzg_hip_recover_poly_from_samples": (i32, [vp, vp, vp, u64, vp]),
+        "kzg_hip_recover_poly_from_samples_batch": (i32, [vp, vp, vp, u64, u64, u64, vp, vp]),
+        "kzg_hip_recover_poly_from_samples_batch_dev": (i32, [vp, vp, vp, u64, u64, u64, vp, vp, vp]),
+        "kzg_hip_zero_poly_via_multiplication_batch": (i32, [vp, vp, vp, u64, u64, vp, vp, vp]),
         "kzg_hip_calibrate": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "kzg_hip_bench_drop_in": (i32, [vp, i32, vp, u64, u64, u32, u32, vp, C.POINTER(C.c_double)]),
         "kzg_hip_coalesce_stats": (i32, [vp, i32, C.POINTER(u64)]),
@@ -350,6 +353,28 @@ class FFTSettings:
             raise KzgError(st, "failed to reconstruct data correctly")
         _chk(st, error_ok=True)
         return out
+
+    def recover_poly_from_samples_batch(self, samples, present):
+        """RecoverPolyFromSamples on every row of samples (batch, n, 4); present: (n,) one mask shared by every row, or (batch, n).  Returns (rows, status):
+        status[b] is OK, ERR_RECOVERY or ERR_BAD_ARG (nothing present), a failed row is zero-filled, a row with nothing missing is copied through"""
+        samples = np.ascontiguousarray(samples, dtype=np.uint64)
+        present = np.ascontiguousarray(present, dtype=np.uint8)
+        batch, n = samples.shape[0], samples.shape[1]
+        if present.shape not in ((n,), (batch, n)):
+            raise KzgPanic(ERR_LEN_MISMATCH, "present must have shape (n,) or (batch, n)")
+        out, status = np.zeros_like(samples), np.zeros(batch, dtype=np.uint8)
+        _chk(lib().kzg_hip_recover_poly_from_samples_batch(self.h, _p(samples), _p(present), 1 if present.ndim == 1 else batch, n, batch, _p(out), _p(status)), error_ok=True)
+        return out, status
+
+    def zero_poly_via_multiplication_batch(self, missing_lists, length):
+        """ZeroPolyViaMultiplication of every erasure set of missing_lists: (zero_evals, zero_polys, status), rows of `length`; status[b] is OK or ERR_BAD_ARG"""
+        lists = [np.ascontiguousarray(m, dtype=np.uint64).reshape(-1) for m in missing_lists]
+        off = np.zeros(len(lists) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([m.shape[0] for m in lists], dtype=np.uint64)
+        flat = np.concatenate(lists + [np.zeros(1, dtype=np.uint64)])      # (never empty: a pointer for a call whose sets are all empty)
+        ze, zp, status = np.zeros((len(lists), length, 4), dtype=np.uint64), np.zeros((len(lists), length, 4), dtype=np.uint64), np.zeros(len(lists), dtype=np.uint8)
+        _chk(lib().kzg_hip_zero_poly_via_multiplication_batch(self.h, _p(flat), _p(off), len(lists), length, _p(ze), _p(zp), _p(status)), error_ok=True)
+        return ze, zp, status
 
     def bench_threads_fft(self, rows, threads, calls):
         """`threads` native host threads x `calls` blocking FFT calls on host buffers (kzg_hip_bench_threads_fft_fr): (calls per second, last results)"""

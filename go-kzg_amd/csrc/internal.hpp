@@ -53,6 +53,23 @@ void launch_fr_scale_by_inv_powers(hipStream_t s, fr *c, const fr *x, uint64_t n
 void launch_zero_eval_direct(hipStream_t s, const fr *expanded, uint64_t stride, const uint64_t *missing, uint64_t n_missing, uint64_t length, fr *zero_eval);
 void launch_fr_scale_by_powers(hipStream_t s, fr *poly, const fr *base, uint64_t n);
 void launch_fr_pointwise(hipStream_t s, const fr *a, const fr *b, const uint8_t *present, fr *out, uint64_t n, int mode, uint32_t *flag);
+// the same over the rows of a chunk: row r evaluates its own erasure list missing[r * list_stride ..) of n_missing[r] entries with correction corr[r]
+uint32_t launch_zero_eval_direct_rows_segs(uint64_t length, uint64_t rows, uint64_t nm_hint);   // wavefronts per point (the corrections depend on it)
+void launch_zero_eval_direct_rows(hipStream_t s, const fr *expanded, uint64_t stride, const uint64_t *missing, uint64_t list_stride, const uint64_t *n_missing, const fr *corr,
+                                  uint32_t segs, uint64_t length, uint64_t rows, fr *zero_eval);
+
+// ---------------- k_recovery.hip ----------------
+// batched erasure recovery (lane bodies: recover_rows.hpp); rows of n values, erasure lists in rows of list_stride entries
+void launch_rr_scan(hipStream_t s, const uint8_t *present, uint64_t n, uint64_t rows, uint64_t *list, uint32_t *count, uint64_t *nm);   // masks -> lists, counts, effective counts
+void launch_rr_corr(hipStream_t s, const uint64_t *nm, uint64_t rows, uint32_t segs, fr *corr);
+void launch_rr_shift_bases(hipStream_t s, const fr &inv5, const fr &five, fr *out);   // out = {5^-1, 5}
+void launch_rr_leaves(hipStream_t s, const fr *expanded, uint64_t stride, const uint64_t *list, uint64_t list_stride, const uint64_t *nm, uint64_t leaves, uint64_t rows, fr *a);
+void launch_rr_unpad(hipStream_t s, const fr *root, uint64_t leaves, const uint64_t *nm, uint64_t length, uint64_t rows, fr *poly);
+void launch_rr_mask_mul(hipStream_t s, const fr *a, const fr *b, uint64_t b_stride, const uint8_t *present, uint64_t p_stride, uint64_t n, uint64_t rows, fr *out);
+void launch_rr_strip_divide(hipStream_t s, const fr *num, const fr *den, fr *out, uint64_t total);   // out = num / den (num null: 1 / den), one inversion per 64
+// status[row] and out[row] from the reconstruction (null: rows are only classified and copied), the samples and the counts; out may be recon
+void launch_rr_finish(hipStream_t s, const fr *recon, const fr *samples, const uint8_t *present, uint64_t p_stride, const uint32_t *count, uint64_t c_stride, uint32_t *flag,
+                      uint64_t n, uint64_t rows, fr *out, uint8_t *status);
 
 // ---------------- k_g1.hip ----------------
 // out[i] = scalars[i * s_stride] * pts[(i % pts_mod)]   (element-wise bls.MulG1; scalars in Montgomery form)

@@ -721,8 +721,8 @@ void launch_fr_scale_by_inv_powers(hipStream_t s, fr *c, const fr *x, uint64_t n
 // lazy subtraction + 153 multiply-adds instead of a canonical subtraction + the 170-multiply-add product with its packing: 1.5x.
 // A point's chain is cut into `segs` pieces, one wavefront of the workgroup each (the missing root of a step stays wave-uniform), multiplied
 // together through LDS at the end: 65 536 points alone are one wavefront per SIMD, and a lone wavefront waits on its own dependent products.
-__global__ void __launch_bounds__(1024) k_zero_eval_direct(const fr *expanded, uint64_t stride, const uint64_t *missing, uint64_t n_missing, uint64_t length,
-                                                           fr *zero_eval, fr corr) {
+__device__ __forceinline__ void zero_eval_direct_body(const fr *expanded, uint64_t stride, const uint64_t *missing, uint64_t n_missing, uint64_t length,
+                                                      fr *zero_eval, const fr &corr) {
     extern __shared__ uint32_t zsh[];                                     // [segs - 1][9][64]
     const uint32_t lane = threadIdx.x & 63, seg = threadIdx.x >> 6, segs = blockDim.x >> 6;
     uint64_t k = blockIdx.x * 64ull + lane;
@@ -748,6 +748,28 @@ __global__ void __launch_bounds__(1024) k_zero_eval_direct(const fr *expanded, u
         acc = frl_mul(o, acc);
     }
     if (blockIdx.x * 64ull + lane < length) zero_eval[k] = frl_canon_lt2r(frl_mul(acc, frl_const_from_kilic(corr)));
+}
+__global__ void __launch_bounds__(1024) k_zero_eval_direct(const fr *expanded, uint64_t stride, const uint64_t *missing, uint64_t n_missing, uint64_t length,
+                                                           fr *zero_eval, fr corr) {
+    zero_eval_direct_body(expanded, stride, missing, n_missing, length, zero_eval, corr);
+}
+// the same over the rows of a chunk (batched recovery): row blockIdx.y has its own erasure list, effective length and correction (recover_rows.hpp).  A row with
+// fewer roots than segments leaves some segments empty: they contribute the image of one and the join's 2^-5, which the row's correction counts.
+__global__ void __launch_bounds__(1024) k_zero_eval_direct_rows(const fr *expanded, uint64_t stride, const uint64_t *missing, uint64_t list_stride, const uint64_t *n_missing,
+                                                                uint64_t length, fr *zero_eval, const fr *corr) {
+    const uint64_t row = blockIdx.y;
+    zero_eval_direct_body(expanded, stride, missing + row * list_stride, n_missing[row], length, zero_eval + row * length, corr[row]);
+}
+uint32_t launch_zero_eval_direct_rows_segs(uint64_t length, uint64_t rows, uint64_t nm_hint) {   // wavefronts per point: aim at 4 per SIMD, as the lone launcher does
+    uint32_t segs = 1;
+    while (segs < 16 && length * rows * segs < 262144 && 2ull * segs <= nm_hint) segs *= 2;
+    return segs;
+}
+void launch_zero_eval_direct_rows(hipStream_t s, const fr *expanded, uint64_t stride, const uint64_t *missing, uint64_t list_stride, const uint64_t *n_missing, const fr *corr,
+                                  uint32_t segs, uint64_t length, uint64_t rows, fr *zero_eval) {
+    if (!length || !rows) return;
+    hipLaunchKernelGGL(k_zero_eval_direct_rows, dim3((uint32_t)((length + 63) / 64), (uint32_t)rows), dim3(64 * segs), (segs - 1) * 9 * 64 * 4, s, expanded, stride, missing,
+                       list_stride, n_missing, length, zero_eval, corr);
 }
 void launch_zero_eval_direct(hipStream_t s, const fr *expanded, uint64_t stride, const uint64_t *missing, uint64_t n_missing, uint64_t length, fr *zero_eval) {
     if (!length) return;

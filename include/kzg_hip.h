@@ -303,6 +303,21 @@ int kzg_hip_zero_poly_via_multiplication(kzg_hip_fft *fs, const uint64_t *missin
  * n samples, present[i] == 0 <=> samples[i] == nil; writes the n reconstructed values.  KZG_HIP_ERR_RECOVERY when a known
  * sample is not reproduced (the reference's error). */
 int kzg_hip_recover_poly_from_samples(kzg_hip_fft *fs, const void *samples_fr, const uint8_t *present, uint64_t n, void *out_fr);
+/* Many rows per call: `batch` rows of n samples, every stage one launch over the rows of a chunk (KZG_HIP_RECOVER_CHUNK_MB).
+ * present_rows == 1: one mask shared by every row (whole columns lost), present_rows == batch: a mask per row.  status[row]: KZG_HIP_OK,
+ * KZG_HIP_ERR_RECOVERY or KZG_HIP_ERR_BAD_ARG (a row with nothing present); a failed row's output is zero-filled, a row with nothing missing is
+ * copied through.  Status and bytes of a row are what kzg_hip_recover_poly_from_samples returns for that row alone.  n not a power of two or wider
+ * than the settings, null pointers and any other present_rows fail the whole call; batch == 0 is KZG_HIP_OK. */
+int kzg_hip_recover_poly_from_samples_batch(kzg_hip_fft *fs, const void *samples_fr, const uint8_t *present, uint64_t present_rows, uint64_t n,
+                                            uint64_t batch, void *out_fr, uint8_t *status);
+/* The same on device-resident rows, ordered on `stream`: erasure lists, counts and statuses are derived on the device, the call never waits for it. */
+int kzg_hip_recover_poly_from_samples_batch_dev(kzg_hip_fft *fs, const void *d_samples_fr, const uint8_t *d_present, uint64_t present_rows, uint64_t n,
+                                                uint64_t batch, void *d_out_fr, uint8_t *d_status, void *stream);
+/* Vanishing polynomials of `batch` ragged erasure sets: row b's indices are missing_indices[offsets[b] .. offsets[b + 1]); rows of `length`
+ * evaluations and coefficients.  status[b]: KZG_HIP_OK (no index: all zeros) or KZG_HIP_ERR_BAD_ARG (as many indices as `length` or more, or an
+ * index >= length: that row is zero-filled, its neighbours are computed). */
+int kzg_hip_zero_poly_via_multiplication_batch(kzg_hip_fft *fs, const uint64_t *missing_indices, const uint64_t *offsets, uint64_t batch,
+                                               uint64_t length, void *out_zero_eval_fr, void *out_zero_poly_fr, uint8_t *status);
 
 /* ---- several GPUs behind ONE handle (SURVEY.md 8b threading row: "multi-GPU handle owns one context per device"; 8e) ----
  * The reference is a single-process library (kzg.go:11-19): a drop-in that uses every GPU of a node does so inside this library.

@@ -117,6 +117,26 @@ class FFTSettings {
         detail::must(st);
         return out;
     }
+    // many rows per call (rows of n = samples.size() / rows values, row-major): present holds one mask of n bytes shared by every row, or one per row.
+    // Returns the rows and one status per row (KZG_HIP_OK, KZG_HIP_ERR_RECOVERY, KZG_HIP_ERR_BAD_ARG for a row with nothing present; failed rows are zero)
+    std::pair<std::vector<Fr>, std::vector<uint8_t>> RecoverPolyFromSamplesBatch(const std::vector<Fr> &samples, const std::vector<uint8_t> &present, uint64_t rows) const {
+        std::vector<Fr> out(samples.size()); std::vector<uint8_t> status(rows);
+        const uint64_t n = rows ? samples.size() / rows : 0;
+        if (!rows) return {out, status};
+        if (samples.size() != n * rows || (present.size() != n && present.size() != samples.size())) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "rows of samples and masks do not match");
+        detail::must(kzg_hip_recover_poly_from_samples_batch(h_, samples.data(), present.data(), present.size() == n ? 1 : rows, n, rows, out.data(), status.data()));
+        return {out, status};
+    }
+    // vanishing polynomials of several erasure sets: (zeroEvals, zeroPolys) in rows of `length`, one status per set
+    std::pair<std::vector<Fr>, std::vector<Fr>> ZeroPolyViaMultiplicationBatch(const std::vector<std::vector<uint64_t>> &missingIndices, uint64_t length,
+                                                                                std::vector<uint8_t> *status = nullptr) const {
+        std::vector<uint64_t> flat, off(1, 0);
+        for (const auto &m : missingIndices) { flat.insert(flat.end(), m.begin(), m.end()); off.push_back(flat.size()); }
+        std::vector<Fr> ev(length * missingIndices.size()), zp(ev.size()); std::vector<uint8_t> st(missingIndices.size());
+        detail::must(kzg_hip_zero_poly_via_multiplication_batch(h_, flat.data(), off.data(), missingIndices.size(), length, ev.data(), zp.data(), st.data()));
+        if (status) *status = st;
+        return {ev, zp};
+    }
     // bls helpers over slices
     std::vector<Fr> FrFrom32(const std::vector<uint8_t> &le32, bool *allOk = nullptr) const {
         std::vector<Fr> out(le32.size() / 32); int ok = 0;
