@@ -51,7 +51,6 @@ extern thread_local std::string g_last_error;   // defined in capi_core.hip
 
 inline bool is_pow2(uint64_t v) { return (v & (v - 1)) == 0; }   // bls.IsPowerOfTwo (bls/globals.go:72-74): true for 0
 inline uint64_t next_pow2(uint64_t v) { if (v == 0) return 1; uint64_t p = 1; while (p < v) p <<= 1; return p; }   // fft.go:11-16
-inline uint32_t ilog2(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
 
 // ---------------------------------------------------------------------------------------------------------
 // handles
@@ -260,7 +259,7 @@ int ensure_fixed_table(kzg_hip_kzg *ks, hipStream_t);   // capi_kzg.hip
 const void *host_mapped_pointer(const void *host, size_t bytes);
 int h2d_copy(void *dst, const void *src, size_t bytes, hipStream_t s);   // capi_kzg.hip: cut at the boundaries of registered ranges   // capi_kzg.hip
 int commit_rows(kzg_hip_kzg *ks, hipStream_t s, const fr *d_sc, uint64_t n, uint64_t batch, g1j *d_out, uint64_t sc_stride = 0, bool to_kilic = true);   // capi_kzg.hip
-double table_budget_gb(const char *env, double cap_gb, double headroom_gb);   // capi_kzg.hip
+double table_budget_gb(knobs::opt_gb env, double cap_gb, double headroom_gb);   // capi_kzg.hip
 int lincomb_points_rows(kzg_hip_points *pts, hipStream_t s, const fr *d_sc, uint64_t n, uint64_t batch, g1j *d_out, uint64_t sc_stride = 0, bool holds_mu = false);   // capi_core.hip
 int lincomb_points_coalesced(kzg_hip_points *pts, const void *scalars_fr, uint64_t n, void *out_g1);   // capi_kzg.hip
 uint32_t fb_windows(uint32_t c);   // capi_kzg.hip

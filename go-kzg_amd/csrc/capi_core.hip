@@ -158,8 +158,7 @@ void *stream_cache_take(hipStream_t s, size_t class_bytes) {
     return p;
 }
 bool stream_cache_give(hipStream_t s, void *p, size_t class_bytes) {
-    static const bool off = [] { const char *e = getenv("KZG_HIP_STREAM_CACHE"); return e && e[0] == '0'; }();   // A/B and test hook
-    if (off) return false;
+    if (!knobs::stream_cache()) return false;   // A/B and test hook
     std::lock_guard<std::mutex> lk(g_sc_mu);
     auto it = g_sc.find(s);
     if (it == g_sc.end()) return false;
@@ -250,8 +249,7 @@ int kzg_hip_fft_fr_batch(kzg_hip_fft *fs, const void *vals_fr, uint64_t n, uint6
 // 12 ms per transform against 19 ms for the 12 launches of the radix-2 network, which are one scalar-multiplication latency each);
 // 0 = the radix-2 network (larger batches fill the chip per stage).  KZG_HIP_G1_FFT = "direct" / "radix2" forces a path (A/B runs).
 uint32_t g1_fft_direct_logr(uint64_t n, uint64_t batch) {
-    static const int forced = [] { const char *e = getenv("KZG_HIP_G1_FFT"); return !e ? 0 : (e[0] == 'd' ? 1 : 2); }();   // (initialised once, thread-safe)
-    if (forced) return forced == 1 ? 4u : 0u;
+    if (const knobs::g1_fft_mode forced = knobs::g1_fft(); forced != knobs::g1_fft_mode::by_size) return forced == knobs::g1_fft_mode::direct ? 4u : 0u;
     if (n < 2) return 0;
     // with four lanes per butterfly (g1_quad.hpp) the radix-2 network beats the direct passes from two transforms on (DAUsingFK20 on 2 / 4 polynomials:
     // 20.8 / 21.0 ms against 23.3 / 30.5 ms); a lone transform stays direct (15.1 ms against 20.7 ms)
@@ -266,8 +264,7 @@ uint32_t g1_fft_direct_logr(uint64_t n, uint64_t batch) {
 bool g1_fft_direct_mode(uint64_t n, uint64_t batch) { return g1_fft_direct_logr(n, batch) != 0; }
 // lanes per (output, term) of a direct pass: as many as keep the pass at one wavefront per SIMD (65 536 lanes)
 int g1_fft_direct_lanes(uint64_t n, uint64_t batch) {
-    static const bool off = [] { const char *e = getenv("KZG_HIP_G1_DIRECT_COOP"); return e && e[0] == '0'; }();
-    if (!g1_quad_enabled() || off) return 1;
+    if (!g1_quad_enabled() || !knobs::g1_direct_coop()) return 1;
     const uint64_t items = (n * batch) << g1_fft_direct_logr(n, batch);
     const uint64_t one_round = device_simd_lanes();
     return items * 4 <= one_round ? 4 : items * 2 <= one_round ? 2 : 1;
@@ -315,10 +312,9 @@ int kzg_hip_fft_g1(kzg_hip_fft *fs, const void *vals_g1, uint64_t n, int inv, vo
 // through the lazy-limb transforms: coefficients (inverse transform), x -> w_2n x (one product per coefficient), values again.  The odd-index
 // evaluations are unique, so this is the reference's result bit for bit.  Other widths and sizes: the recursion itself, stage by stage.
 int das_ext_rows(kzg_hip_fft *fs, hipStream_t s, fr *d, uint64_t n, uint64_t batch) {
-    static const bool radix2_forced = [] { const char *e = getenv("KZG_HIP_FR_FFT"); return e && !strcmp(e, "radix2"); }();
     // (... and launches of 2^20 values in rows of at most 64: the short transforms share workgroups, k_fr_fft_small)
-    const bool long_rows = n >= fr4::N && n <= 16 * (uint64_t)fr4::N, short_rows = n >= 4 && n <= 64 && n * batch >= (256ull * fr4::N);   // (measured: 8 values 3.8 -> 0.5 ns, 64 values 8.7 -> 5.7 ns per row; no gain from 128 on)
-    if (2 * n == fs->W && (long_rows || short_rows) && fs->d_tw4096[0] && !radix2_forced) {
+    const bool long_or_short = n >= fr4::N || n <= 64;   // (measured: 8 values 3.8 -> 0.5 ns, 64 values 8.7 -> 5.7 ns per row; no gain from 128 on)
+    if (2 * n == fs->W && long_or_short && fr_fft_lazy_sizes(n, batch) && fs->d_tw4096[0]) {
         dtmp<fr> d_c(s);
         CHK(d_c.alloc(n * batch));
         fr_fft_rows(fs, s, d, n, n, d_c.p, n, batch, 1);
@@ -476,7 +472,7 @@ int kzg_hip_points_new(kzg_hip_fft *fs, const void *points_g1, uint64_t n, kzg_h
         CHK(kzg_settings_build(fs, points_g1, n, &own->ks));
         // budget of the set's fixed-base table: KZG_HIP_POINTS_FB_BUDGET_GB, else min(32 GB, free HBM - 24 GB) at creation (4096 points: 13-bit windows,
         // 20 of them, 32 GB); 0 keeps the set on the bucket pipeline.  kzg_hip_points_set_table_budget_gb changes it per set.
-        own->ks->budget_gb = table_budget_gb("KZG_HIP_POINTS_FB_BUDGET_GB", 32.0, 24.0);
+        own->ks->budget_gb = table_budget_gb(knobs::points_fb_budget_gb(), 32.0, 24.0);
     }
     *out = own.release();
     return KZG_HIP_OK;
@@ -571,11 +567,9 @@ uint64_t lincomb_fingerprint(const uint8_t *p, uint64_t n) {
     if (bytes > head) eat(p + bytes - head, head);
     return h;
 }
-bool lincomb_promotion_enabled() { static const bool on = [] { const char *e = getenv("KZG_HIP_LINCOMB_PROMOTE"); return !(e && e[0] == '0'); }(); return on; }
-uint32_t lincomb_promote_after() { static const uint32_t v = [] { const char *e = getenv("KZG_HIP_LINCOMB_PROMOTE_AFTER"); long x = e ? atol(e) : 2; return (uint32_t)(x < 1 ? 1 : x > 1000 ? 1000 : x); }(); return v; }
 // the cached set for these points if they are a promoted set (or become one with this call); null: take the one-shot path
 std::shared_ptr<kzg_hip_points> lincomb_promoted_set(kzg_hip_fft *fs, const void *points_g1, uint64_t n) {
-    if (!lincomb_promotion_enabled() || n < 64 || n > (1u << 20)) return nullptr;
+    if (!knobs::lincomb_promote() || n < 64 || n > (1u << 20)) return nullptr;
     const uint8_t *pb = (const uint8_t *)points_g1;
     const size_t bytes = (size_t)n * sizeof(g1j);
     const uint64_t fpv = lincomb_fingerprint(pb, n);
@@ -610,7 +604,7 @@ std::shared_ptr<kzg_hip_points> lincomb_promoted_set(kzg_hip_fft *fs, const void
         return set;
     }
     if (hit->copy->size() != bytes || memcmp(hit->copy->data(), pb, bytes) != 0) return nullptr;   // same fingerprint, different points (or changed in place): one-shot
-    if (++hit->sightings <= lincomb_promote_after() + 0u) return nullptr;
+    if (++hit->sightings <= knobs::lincomb_promote_after()) return nullptr;
     // promote: build the cached set from the copy (outside the lock: other sets keep being served)
     hit->building = true;
     std::vector<std::shared_ptr<kzg_hip_points>> evicted;                  // freed outside the lock, after their last call in flight

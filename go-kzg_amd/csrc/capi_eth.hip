@@ -218,8 +218,7 @@ int kzg_hip_eth_compute_kzg_proof(kzg_hip_eth *eth, const void *poly_fr, uint64_
             // (A/B hook: measured 0.314 against 0.309 ms in place for a lone call -- the copy costs what it saves).
             dtmp<fr> d_rows(s);
             const fr *src = (const fr *)dp_in;
-            static const uint64_t stage_rows = [] { const char *e = getenv("KZG_HIP_ETH_STAGE_ROWS"); return e ? (uint64_t)atol(e) : 0ull; }();
-            if (rows <= stage_rows) {
+            if (rows <= knobs::eth_stage_rows()) {
                 CHK(d_rows.alloc(rows * stride));
                 HIPCHK(hipMemcpyAsync(d_rows.p, b.h_in, rows * co->in_row_bytes(), hipMemcpyHostToDevice, s));
                 src = d_rows.p;

@@ -30,7 +30,7 @@ static int fk20_core_new(kzg_hip_kzg *ks, uint64_t n2, uint64_t l, fk20_core *c)
         // (plain: c = 13, 20, 32 GB);  scale 13 (8192 points): c = 13, 2 x 10, 32 GB (plain: c = 12, 22, 35 GB);  scale 16, l = 16 (65 536 points): c = 10, 2 x 13, 42 GB
         // (plain: c = 9, 29, 47 GB).
         // An allocation failure falls back to the next smaller window and finally to the table-free double-and-add path.
-        double budget_gb = table_budget_gb("KZG_HIP_FK20_FB_BUDGET_GB", 48.0, 12.0);
+        double budget_gb = table_budget_gb(knobs::fk20_fb_budget_gb(), 48.0, 12.0);
         uint64_t npts = l * k2;
         const bool glv = fb_glv_enabled();
         dtmp<g1a> d_fa(s);
@@ -103,9 +103,8 @@ int fk20_finish(fk20_core *c, hipStream_t s, const g1j *d_hext, uint64_t batch, 
 // the inverse transform in one kernel (k_fb_direct_pass1: every term of that pass is a fixed-base product, nwin additions instead of a variable-base
 // multiplication), the remaining passes continue from there.  KZG_HIP_FK20_PASS1=0 turns it off (tests compare both).
 static bool fk20_pass1_fused_ok(const fk20_core *c, uint64_t batch) {
-    static const bool off = [] { const char *e = getenv("KZG_HIP_FK20_PASS1"); return e && e[0] == '0'; }();
     const uint64_t k2 = 2 * c->k;
-    return !off && c->l == 1 && c->d_files_fb && k2 >= 32 && g1_fft_direct_mode(k2, batch) && g1_fft_direct_logr(k2, batch) == 4;
+    return knobs::fk20_pass1() && c->l == 1 && c->d_files_fb && k2 >= 32 && g1_fft_direct_mode(k2, batch) && g1_fft_direct_logr(k2, batch) == 4;
 }
 static int fk20_run_pass1_fused(fk20_core *c, hipStream_t s, const fr *d_poly, uint64_t poly_stride, uint64_t n, uint64_t batch, int da, int bit_reverse, g1j *d_out) {
     kzg_hip_fft *fs = c->ks->fs;
@@ -126,9 +125,8 @@ static int fk20_run_pass1_fused(fk20_core *c, hipStream_t s, const fr *d_poly, u
 // The plain form (FK20Single, fk20_single.go:122-137: proofs = FFT_G1(h) on k points) continues from the EVEN positions of that layout, which
 // are h[:k] in k-point bit-reversed order.
 static bool fk20_fused_ok(const fk20_core *c, uint64_t batch, int da) {
-    static const bool off = [] { const char *e = getenv("KZG_HIP_FK20_FUSE"); return e && e[0] == '0'; }();
     const uint64_t k2 = 2 * c->k;
-    return !off && c->l == 1 && c->d_files_fb && k2 >= 8 && !g1_fft_direct_mode(k2, batch) && (da || !g1_fft_direct_mode(c->k, batch));
+    return knobs::fk20_fuse() && c->l == 1 && c->d_files_fb && k2 >= 8 && !g1_fft_direct_mode(k2, batch) && (da || !g1_fft_direct_mode(c->k, batch));
 }
 static int fk20_run_fused(fk20_core *c, hipStream_t s, const fr *d_poly, uint64_t poly_stride, uint64_t n, uint64_t batch, int da, int bit_reverse, g1j *d_out) {
     kzg_hip_fft *fs = c->ks->fs;
@@ -159,8 +157,7 @@ static int fk20_run_fused(fk20_core *c, hipStream_t s, const fr *d_poly, uint64_
 // holds one twiddle ((n / 2 / m) * batch a multiple of 64, or >= 256), so 17 or 31 polynomials took 45.5 / 45.9 ms against 36.5 for 32, and 63 took
 // 79.9 against 64.7 for 64.  Up to 32 polynomials a stage is one wavefront per SIMD whatever the count; beyond, rows are only added where they cost under 3 %.
 static uint64_t fk20_padded_batch(uint64_t batch) {
-    static const bool off = [] { const char *e = getenv("KZG_HIP_FK20_PAD"); return e && e[0] == '0'; }();
-    if (off) return batch;
+    if (!knobs::fk20_pad()) return batch;
     if (batch > 16 && batch < 32) return 32;
     if (batch > 32 && (batch & 7)) {                          // beyond one wavefront per SIMD padding is work: only where it is < 3 % (63 -> 64: 79.9 -> 66.5 ms,
         const uint64_t p = (batch + 7) & ~7ull;                 // 127 -> 128: 140 -> 121 ms; 65 -> 72 and 100 -> 104 measured slower)

@@ -47,8 +47,8 @@ void kzg_hip_kzg_settings_free(kzg_hip_kzg *ks) {
 // number of signed c-bit windows of a canonical scalar (< r < 2^255): ceil(255 / c), plus one only if the top window's
 // digit (top bits of r - 1, plus the incoming carry) can exceed 2^(c-1) and carry out (c = 15 carries: 18 windows, c = 16 does not: 16)
 // table budget in GB: the environment override, else min(cap, free HBM - headroom)
-double table_budget_gb(const char *env, double cap_gb, double headroom_gb) {
-    if (const char *e = getenv(env)) return atof(e);
+double table_budget_gb(knobs::opt_gb env, double cap_gb, double headroom_gb) {
+    if (env.set) return env.gb;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 0.0;
     double g = (double)free_b / 1e9 - headroom_gb;
@@ -77,14 +77,11 @@ uint32_t fb_windows(uint32_t c) {
 // windows of the GLV walk: both halves of a split scalar are below 2^126.5 (glv_split_signed), so the top signed digit cannot carry out as soon as
 // c * nwin >= 128
 uint32_t fb_windows_glv(uint32_t c) { return (128 + c - 1) / c; }
-bool fb_glv_enabled() {
-    static const bool on = [] { const char *e = getenv("KZG_HIP_FB_GLV"); return !(e && !strcmp(e, "0")); }();   // "0": the round-1..4 layout (one window per c bits of the whole scalar), A/B runs and tests
-    return on;
-}
+bool fb_glv_enabled() { return knobs::fb_glv(); }
 int ensure_fixed_table(kzg_hip_kzg *ks, hipStream_t) {
     if (ks->d_fixed || ks->fixed_plan.c == 0xffffffffu) return KZG_HIP_OK;
     hipStream_t s = ks->fs->stream;
-    double budget_gb = ks->budget_gb >= 0.0 ? ks->budget_gb : table_budget_gb("KZG_HIP_FB_BUDGET_GB", FB_DEFAULT_BUDGET_GB, 24.0);
+    double budget_gb = ks->budget_gb >= 0.0 ? ks->budget_gb : table_budget_gb(knobs::fb_budget_gb(), FB_DEFAULT_BUDGET_GB, 24.0);
     if (ks->n_setup < 64) { ks->fixed_plan.c = 0xffffffffu; return KZG_HIP_OK; }   // classic path only
     const bool glv = fb_glv_enabled();
     for (uint32_t c = 16; c >= 5; c--) {
@@ -262,8 +259,7 @@ int kzg_hip_commit_to_poly_batch(kzg_hip_kzg *ks, const void *coeffs_fr, uint64_
         HIPCHK(hipStreamSynchronize(s));                     // d_sc was allocated in order on s: make it visible to the copy stream
         // The copy of the FIRST chunk overlaps with nothing, so the schedule ramps up: 64 blobs, then 192, then `chunk` at a time (KZG_HIP_UPLOAD_RAMP=0: equal
         // chunks, as through round 5) -- the walk starts after 8 MiB instead of 64 MiB of pageable copy.
-        static const bool ramp_on = [] { const char *e = getenv("KZG_HIP_UPLOAD_RAMP"); return !(e && e[0] == '0'); }();
-        const bool ramp = ramp_on && batch >= 1024;          // (measured: 1024 blobs 78.5 -> 83.9 k/s, 4096 blobs 86.1 -> 86.9 k/s; 512 blobs are better off with two equal chunks: 79.4 vs 76.5 k/s)
+        const bool ramp = knobs::upload_ramp() && batch >= 1024;          // (measured: 1024 blobs 78.5 -> 83.9 k/s, 4096 blobs 86.1 -> 86.9 k/s; 512 blobs are better off with two equal chunks: 79.4 vs 76.5 k/s)
         int slot = 0;
         uint64_t step = 0;
         for (uint64_t b0 = 0, cnt = 0; b0 < batch; b0 += cnt, slot ^= 1, step++) {
@@ -284,10 +280,7 @@ int kzg_hip_commit_to_poly_batch(kzg_hip_kzg *ks, const void *coeffs_fr, uint64_
     return KZG_HIP_OK;
 }
 // ---- one-polynomial calls: concurrent callers on a handle are merged into batched launches (coalesce.hpp) ----
-bool coalescing_enabled() {
-    static const bool on = [] { const char *e = getenv("KZG_HIP_COALESCE"); return !(e && e[0] == '0'); }();
-    return on;
-}
+bool coalescing_enabled() { return knobs::coalesce(); }
 // rows per staging buffer: as many as fit 32 MiB of pinned memory per direction, within [4, 256]
 static uint64_t coalesce_rows(size_t in_row, size_t out_row) {
     size_t row = in_row > out_row ? in_row : out_row;
@@ -330,7 +323,7 @@ int kzg_hip_commit_to_poly(kzg_hip_kzg *ks, const void *coeffs_fr, uint64_t n, v
         void *dp_out = nullptr;
         HIPCHK(hipHostGetDevicePointer(&dp_out, b.h_out, 0));
         g1j *d_out = (g1j *)dp_out;
-        static const bool trace = getenv("KZG_HIP_COALESCE_TRACE") != nullptr;      // phase times on stderr (adds two synchronisations)
+        const bool trace = knobs::coalesce_trace();     // phase times on stderr (adds two synchronisations)
         const auto t0 = std::chrono::steady_clock::now();
         // Uniform rows (the normal case: every caller commits a full blob) are read IN PLACE from the pinned staging buffer: each
         // scalar is loaded exactly once by the table walk, so the 128 KiB per blob stream over PCIe under the walk's own latency

@@ -60,7 +60,7 @@ rccl_api *rccl_bind(std::string *why) {
     std::lock_guard<std::mutex> lk(mu);
     if (!tried) {
         tried = true;
-        const char *names[] = {getenv("KZG_HIP_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+        const char *names[] = {knobs::rccl_lib(), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
         for (const char *nm : names) {
             if (!nm || !*nm) continue;
             api.h = dlopen(nm, RTLD_NOW | RTLD_LOCAL);
@@ -142,8 +142,8 @@ struct kzg_hip_multi {
     int tkind = T_PEER;
     std::string transport = "peer-copy", transport_note, self_test;
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;   // pinned, portable: the host-staged exchange
-    unsigned fault = 0;                    // KZG_HIP_MULTI_FAULT bits (tests)
-    long probe_timeout_ms = 10000;         // deadline of one self-test exchange (KZG_HIP_MULTI_PROBE_TIMEOUT_MS)
+    unsigned fault = knobs::multi_fault();                     // FAULT_* bits (tests: make a leg of the exchange fail so that the fall-backs run on one GPU)
+    long probe_timeout_ms = knobs::multi_probe_timeout_ms();   // deadline of one self-test exchange
     struct abandoned_t { int device; hipStream_t s; hipEvent_t ev; uint8_t *arena; };
     std::vector<abandoned_t> abandoned;    // streams / events / arenas of entries whose probe timed out: never synchronised
     uint32_t *h_spin_flag = nullptr;       // pinned, mapped: what the injected "hang" kernels spin on
@@ -151,7 +151,6 @@ struct kzg_hip_multi {
     std::mutex mu;                         // sharded calls (collectives) on a handle run one at a time
     std::atomic<uint64_t> n_allgather{0};  // exchanges performed (tests and bench read it)
 };
-enum { FAULT_RCCL = 1, FAULT_RCCL_CORRUPT = 2, FAULT_PEER = 4, FAULT_PEER_CORRUPT = 8, FAULT_RCCL_HANG = 16, FAULT_PEER_HANG = 32, FAULT_PEER_STUCK = 64, FAULT_RCCL_BLOCK = 128, FAULT_RCCL_INIT_BLOCK = 256 };
 struct kzg_hip_multi_eth { kzg_hip_multi *m = nullptr; std::vector<kzg_hip_eth *> eth; uint64_t n = 0; };
 struct kzg_hip_multi_fk20s { kzg_hip_multi *m = nullptr; std::vector<kzg_hip_fk20s *> fk; uint64_t n2 = 0; };
 struct kzg_hip_multi_fk20m { kzg_hip_multi *m = nullptr; std::vector<kzg_hip_fk20m *> fk; uint64_t n2 = 0, l = 1; };
@@ -578,7 +577,7 @@ int sharded_g1_fft(kzg_hip_multi *m, std::vector<mtmp> &tmp, const std::vector<c
 }
 
 bool sharded_fft_default(const kzg_hip_multi *m) {
-    if (const char *e = getenv("KZG_HIP_MULTI_FFT")) return !strcmp(e, "sharded");
+    if (const int forced = knobs::multi_fft(); forced >= 0) return forced == 1;
     if (m->fft_mode >= 0) return m->fft_mode == 1;
     return m->d.size() >= 4;   // two devices halve one of three launches of a lone transform and pay two exchanges for it
 }
@@ -665,21 +664,7 @@ int kzg_hip_multi_settings_new(const int *devices, uint32_t n_devices, unsigned 
     std::unique_ptr<kzg_hip_multi, void (*)(kzg_hip_multi *)> owner(new kzg_hip_multi, kzg_hip_multi_settings_free);
     kzg_hip_multi *m = owner.get();
     m->d.resize(n_devices);
-    if (const char *t = getenv("KZG_HIP_MULTI_PROBE_TIMEOUT_MS")) { long v = atol(t); if (v >= 10 && v <= 600000) m->probe_timeout_ms = v; }
     for (uint32_t i = 0; i < n_devices; i++) { m->d[i].device = devices[i]; m->d[i].arena.device = devices[i]; }
-    if (const char *f = getenv("KZG_HIP_MULTI_FAULT")) {   // tests: make a leg of the exchange fail so that the fall-backs run on one GPU
-        std::string fs(f);
-        auto has = [&](const char *w) { size_t at = 0; const size_t n = strlen(w); while ((at = fs.find(w, at)) != std::string::npos) { const size_t e = at + n; if ((at == 0 || fs[at - 1] == ',') && (e == fs.size() || fs[e] == ',')) return true; at = e; } return false; };
-        if (has("rccl")) m->fault |= FAULT_RCCL;
-        if (has("rccl-corrupt")) m->fault |= FAULT_RCCL_CORRUPT;
-        if (has("peer")) m->fault |= FAULT_PEER;
-        if (has("peer-corrupt")) m->fault |= FAULT_PEER_CORRUPT;
-        if (has("rccl-hang")) m->fault |= FAULT_RCCL_HANG;
-        if (has("rccl-block")) m->fault |= FAULT_RCCL_BLOCK;            // the RCCL calls of the probe block on the HOST side (the helper thread sleeps three deadlines)
-        if (has("rccl-init-block")) m->fault |= FAULT_RCCL_INIT_BLOCK;  // ncclCommInitAll does not return in time
-        if (has("peer-hang")) m->fault |= FAULT_PEER_HANG;
-        if (has("peer-stuck")) m->fault |= FAULT_PEER_HANG | FAULT_PEER_STUCK;   // ... and is NOT let go after its streams were abandoned: stuck until the kernel's own clock runs out
-    }
     try {   // one host thread per further entry, for the lifetime of the handle; a thread that cannot be started fails the constructor cleanly
         for (uint32_t i = 1; i < n_devices; i++) {
             m->workers.emplace_back(new dev_worker);
@@ -705,9 +690,9 @@ int kzg_hip_multi_settings_new(const int *devices, uint32_t n_devices, unsigned 
     bool distinct = true;
     for (uint32_t i = 0; i < n_devices; i++) for (uint32_t j = 0; j < i; j++) if (devices[i] == devices[j]) distinct = false;
     enable_peer_access(m);
-    const char *force = getenv("KZG_HIP_MULTI_TRANSPORT");
-    const bool want_rccl = force ? !strcmp(force, "rccl") && distinct : (distinct && n_devices >= 2);
-    if (force && !strcmp(force, "host")) m->tkind = T_HOST;
+    const knobs::transport_mode force = knobs::multi_transport();
+    const bool want_rccl = distinct && (force == knobs::transport_mode::by_devices ? n_devices >= 2 : force == knobs::transport_mode::rccl);
+    if (force == knobs::transport_mode::host) m->tkind = T_HOST;
     if (want_rccl) {
         std::string why;
         rccl_api *api = rccl_bind(&why);

@@ -30,9 +30,9 @@ static int zero_poly_tree(kzg_hip_fft *fs, hipStream_t s, const uint64_t *d_miss
     return KZG_HIP_OK;
 }
 static int zero_poly_dev(kzg_hip_fft *fs, hipStream_t s, const uint64_t *d_missing, uint64_t n_missing, uint64_t length, fr *d_eval, fr *d_poly) {
-    static const int forced = [] { const char *e = getenv("KZG_HIP_ZERO_POLY"); return !e ? 0 : !strcmp(e, "direct") ? 1 : !strcmp(e, "tree") ? 2 : 0; }();
+    const knobs::zero_poly_mode forced = knobs::zero_poly_once();
     // measured crossover (half of the domain missing): 8192 points, where both take 0.7 ms; 32 768 points: 4.9 ms direct, 1.2 ms through the tree
-    if (forced == 2 || (forced == 0 && n_missing >= 1024 && n_missing * length >= (1ull << 26))) return zero_poly_tree(fs, s, d_missing, n_missing, length, d_eval, d_poly);
+    if (forced == knobs::zero_poly_mode::tree || (forced == knobs::zero_poly_mode::by_size && n_missing >= 1024 && n_missing * length >= (1ull << 26))) return zero_poly_tree(fs, s, d_missing, n_missing, length, d_eval, d_poly);
     launch_zero_eval_direct(s, fs->d_expanded, fs->W / length, d_missing, n_missing, length, d_eval);
     fr_fft_rows(fs, s, d_eval, length, length, d_poly, length, 1, 1);     // coefficients: degree n_missing < length
     HIPCHK(hipGetLastError());
@@ -109,10 +109,6 @@ int kzg_hip_recover_poly_from_samples(kzg_hip_fft *fs, const void *samples_fr, c
 // Nothing below reads device memory on the host: erasure lists, counts and statuses are derived on the device, so the _dev form enqueues and returns.
 static_assert(rr::ST_OK == KZG_HIP_OK && rr::ST_BAD_ARG == KZG_HIP_ERR_BAD_ARG && rr::ST_RECOVERY == KZG_HIP_ERR_RECOVERY, "status bytes are the header's codes");
 
-static int zero_poly_forced() {   // read per call: a measurement switches between the two constructions in one process
-    const char *e = getenv("KZG_HIP_ZERO_POLY");
-    return !e ? 0 : !strcmp(e, "direct") ? 1 : !strcmp(e, "tree") ? 2 : 0;
-}
 // Which construction a chunk takes.  nm: the longest erasure list of the chunk where the host knows it, half of the domain where it does not.  Measured
 // (profiles/recovery_batch.md, half of the domain missing, whole calls from host buffers): at 4096 points direct evaluation takes 0.34 ms + 62 us per row, the tree
 // 0.54 ms + 11 us per row -- its launches are shared by all rows of the chunk -- so they cross at 4 rows (2^25 direct products), and at 16 / 64 / 256 rows the tree
@@ -121,14 +117,11 @@ static int zero_poly_forced() {   // read per call: a measurement switches betwe
 constexpr uint64_t ZERO_ROWS_TREE_FROM_NM = 256;          // not measured: below this a row's chain (nm products per point) is shorter than the tree's ~10 transforms (~60 per point)
 constexpr uint64_t ZERO_ROWS_TREE_FROM_PRODUCTS = 1ull << 25;   // direct products of the whole chunk from which the tree wins
 static bool zero_rows_use_tree(uint64_t nm, uint64_t length, uint64_t rows) {
-    const int forced = zero_poly_forced();
-    if (forced) return forced == 2;
+    if (const knobs::zero_poly_mode forced = knobs::zero_poly_per_call(); forced != knobs::zero_poly_mode::by_size) return forced == knobs::zero_poly_mode::tree;
     return nm >= ZERO_ROWS_TREE_FROM_NM && nm * length * rows >= ZERO_ROWS_TREE_FROM_PRODUCTS;
 }
 static uint64_t recover_chunk_rows(uint64_t n) {          // whole rows per chunk under KZG_HIP_RECOVER_CHUNK_MB (fractions allowed: tests force chunks of a few rows)
-    const char *cenv = getenv("KZG_HIP_RECOVER_CHUNK_MB");
-    const double cmb = cenv ? atof(cenv) : 0.0;
-    const uint64_t budget = (uint64_t)((cmb > 0.0 ? cmb : 2048.0) * 1048576.0);
+    const uint64_t budget = (uint64_t)(knobs::recover_chunk_mb() * 1048576.0);
     const uint64_t per_row = 8 * sizeof(fr) * std::max<uint64_t>(n, ZERO_TREE_LEAF);   // six temporaries, the staged samples, list + mask + flags
     return std::min<uint64_t>(std::max<uint64_t>(budget / per_row, 1), 32768);           // (a row is a blockIdx.y of the direct evaluation)
 }

@@ -338,13 +338,10 @@ int kzg_hip_eth_verify_aggregate_kzg_proof_batch(kzg_hip_eth *eth, const void *b
     if (total && (!blobs_le32 || !commitments48)) return KZG_HIP_ERR_BAD_ARG;
     // where the transcripts are hashed: the device takes the same 28 ms for 1 or 4096 chains of four blobs, a host thread 0.23 ms per such
     // sidecar: the measured curves cross between 128 and 192 sidecars (profiles/verify_aggregate.md)
-    const char *tenv = getenv("KZG_HIP_ETH_TRANSCRIPT");                          // read per call: a measurement switches between the two in one process
-    const int forced = !tenv ? 0 : !strcmp(tenv, "host") ? 1 : !strcmp(tenv, "device") ? 2 : 0;
+    const knobs::transcript_mode forced = knobs::eth_transcript();
     constexpr uint64_t TRANSCRIPT_DEVICE_FROM = 176;
-    const bool on_device = forced ? forced == 2 : sidecars >= TRANSCRIPT_DEVICE_FROM;
-    const char *cenv = getenv("KZG_HIP_ETH_VERIFY_CHUNK_MB");                    // (fractions allowed: tests force chunks of a few small blobs)
-    const double cmb = cenv ? atof(cenv) : 0.0;
-    const uint64_t budget = (uint64_t)((cmb > 0.0 ? cmb : 4096.0) * 1048576.0);
+    const bool on_device = forced == knobs::transcript_mode::by_count ? sidecars >= TRANSCRIPT_DEVICE_FROM : forced == knobs::transcript_mode::device;
+    const uint64_t budget = (uint64_t)(knobs::eth_verify_chunk_mb() * 1048576.0);   // (fractions allowed: tests force chunks of a few small blobs)
     constexpr uint64_t CHECKS = 8192;                                            // per pairing launch, as kzg_hip_pairings_verify_batch
     const uint8_t *blobs = (const uint8_t *)blobs_le32, *comms = (const uint8_t *)commitments48, *proofs = (const uint8_t *)proofs48;
 

@@ -17,7 +17,7 @@
 // (64 threads 51 k commitments/s, 256 threads 38 k/s).  Now a call is: fetch_add on the open buffer's state word, memcpy, fetch_add on its
 // `ready` counter, futex sleep -- the mutex is taken twice per BATCH (close + open the next buffer; recycle).
 //
-// One batch is in flight up to ~96 concurrent callers (KZG_COALESCE_CALLERS_PER_BATCH; 48 for the FK20 pipelines), up to MAX_EXEC (on separate streams) beyond: the end of a batch (reduction
+// One batch is in flight up to ~96 concurrent callers (the compile-time KZG_COALESCE_CALLERS_PER_BATCH, at run time KZG_HIP_COALESCE_PER_BATCH; 48 for the FK20 pipelines), up to MAX_EXEC (on separate streams) beyond: the end of a batch (reduction
 // trees, one inversion per polynomial) is latency-bound and uses a fraction of the CUs, so with hundreds of callers the next batch's
 // table walk overlaps it.  The executing function is supplied by the handle (commit / proof / FK20); everything here is host-side C++.
 //
@@ -27,6 +27,7 @@
 // with a handful of callers the batch is back before a park / wake round trip would be, with hundreds the spinners would only take the
 // cores from the row copies.  (Linux only, like ROCm.)
 #pragma once
+#include "knobs.hpp"
 #ifndef KZG_COALESCE_SIM
 #include <hip/hip_runtime.h>
 void stream_cache_own(hipStream_t s);      // capi_core.hip: small stream-ordered temporaries of library-owned streams are recycled per stream
@@ -99,18 +100,14 @@ class coalescer {
     // must block until the results are in host memory; returns a status that every request of the batch receives
     using exec_fn = std::function<int(coalesce_buf &, uint64_t batch)>;
 
-    // callers_per_batch: concurrent callers per batch in flight (0: KZG_COALESCE_CALLERS_PER_BATCH).  The table walk of a commitment wants ONE batch for 64 callers
+    // callers_per_batch: concurrent callers per batch in flight (0: the compile-time KZG_COALESCE_CALLERS_PER_BATCH); the environment's KZG_HIP_COALESCE_PER_BATCH overrides both.  The table walk of a commitment wants ONE batch for 64 callers
     // (96); pipelines whose launches fill the chip from ~32 polynomials on and whose batches take tens of milliseconds (FK20) run two half batches side by side (48).
     coalescer(int device, size_t in_row_bytes, size_t out_row_bytes, uint64_t max_batch, int callers_per_batch = 0)
         : device_(device), in_row_(in_row_bytes), out_row_(out_row_bytes), max_batch_(max_batch) {
-        if (callers_per_batch > 0) per_batch_ = callers_per_batch;
-        if (const char *e = getenv("KZG_HIP_COALESCE_US")) window_us_ = atol(e);
-        if (const char *e = getenv("KZG_HIP_COALESCE_EXEC")) { max_exec_ = atoi(e); if (max_exec_ < 1) max_exec_ = 1; if (max_exec_ > NBUF - 1) max_exec_ = NBUF - 1; }
-        if (const char *e = getenv("KZG_HIP_COALESCE_SPIN_US")) spin_us_ = atol(e);
-        if (const char *e = getenv("KZG_HIP_COALESCE_PER_BATCH")) { per_batch_ = atoi(e); if (per_batch_ < 1) per_batch_ = 1; }
+        per_batch_ = knobs::coalesce_per_batch(callers_per_batch > 0 ? callers_per_batch : KZG_COALESCE_CALLERS_PER_BATCH);
     }
     ~coalescer() {
-        if (getenv("KZG_HIP_COALESCE_STATS") && batches_)
+        if (knobs::coalesce_stats() && batches_)
             fprintf(stderr, "[coalescer] %llu requests in %llu batches (avg %.1f), per batch: %.3f ms executing, %.3f ms waiting for a device slot, %.3f ms gathering callers, %.3f ms waiting for row copies\n",
                     (unsigned long long)requests_.load(), (unsigned long long)batches_.load(), (double)requests_.load() / batches_.load(), exec_ns_.load() * 1e-6 / batches_.load(),
                     slot_ns_.load() * 1e-6 / batches_.load(), gather_ns_.load() * 1e-6 / batches_.load(), ready_ns_.load() * 1e-6 / batches_.load());
@@ -209,11 +206,9 @@ class coalescer {
         stream_cache_own(b.stream);
 #else
         // (simulation: KZG_COALESCE_SIM_MAX_BUFS staging buffers can be allocated, the next allocation fails -- pinned-memory pressure)
-        if (const char *e = getenv("KZG_COALESCE_SIM_MAX_BUFS")) {
-            int have = 0;
-            for (auto &x : bufs_) have += x.h_in != nullptr;
-            if (have >= atoi(e)) return false;
-        }
+        int have = 0;
+        for (auto &x : bufs_) have += x.h_in != nullptr;
+        if (have >= knobs::coalesce_sim_max_bufs()) return false;
         b.h_in = (uint8_t *)malloc(in_row_ * max_batch_); b.h_out = (uint8_t *)malloc(out_row_ * max_batch_); b.h_meta = (coalesce_row *)malloc(sizeof(coalesce_row) * max_batch_);
 #endif
         return true;
@@ -372,16 +367,16 @@ class coalescer {
     std::atomic<uint32_t> open_seq_{0};  // futex word: bumped whenever open_ changes
     std::atomic<int> executing_{0};      // batches that hold a device slot
     std::atomic<uint32_t> slot_word_{0}; // futex word: bumped when a slot is released
-    int max_exec_ = MAX_EXEC;            // upper bound (KZG_HIP_COALESCE_EXEC)
+    int max_exec_ = knobs::coalesce_exec(MAX_EXEC, NBUF - 1);   // upper bound
     std::atomic<int> exec_limit_{1};     // batches allowed in flight right now: 1 .. max_exec_ by the number of concurrent callers
     std::atomic<uint32_t> inside_{0};    // callers currently inside submit()
     std::atomic<uint32_t> inside_max_{0};// its maximum since the last batch was formed
     uint32_t peak_ = 0;                  // decaying maximum of inside_: the concurrency the gather targets are derived from (under mu_)
     long last_close_ns_ = 0;             // when the previous batch's leader got its slot (under mu_)
     std::atomic<int> spinners_{0};
-    long window_us_ = 150;               // upper bound of the gather wait (KZG_HIP_COALESCE_US; 0 disables)
-    long spin_us_ = 40;                  // a follower's spin before it parks (KZG_HIP_COALESCE_SPIN_US; 0 disables)
-    int per_batch_ = KZG_COALESCE_CALLERS_PER_BATCH;   // concurrent callers per batch in flight (KZG_HIP_COALESCE_PER_BATCH)
+    long window_us_ = knobs::coalesce_us();        // upper bound of the gather wait (0 disables)
+    long spin_us_ = knobs::coalesce_spin_us();     // a follower's spin before it parks (0 disables)
+    int per_batch_;                      // concurrent callers per batch in flight (set by the constructor)
     std::atomic<uint64_t> batches_{0}, requests_{0};   // statistics (KZG_HIP_COALESCE_STATS=1 prints them when the handle is freed)
     std::atomic<long> exec_ns_{0}, slot_ns_{0}, gather_ns_{0}, ready_ns_{0};
     std::atomic<uint64_t> peak_seen_{0}; // largest concurrency estimate a leader ever used (statistics)

@@ -4,8 +4,6 @@
 #pragma once
 #include "internal.hpp"
 #include "g1_quad.hpp"
-#include <stdlib.h>
-#include <string.h>
 
 namespace kzg {
 
@@ -14,7 +12,6 @@ namespace kzg {
 #endif
 struct g1jq_slot { uint32_t w[39]; uint32_t inf; uint32_t pad; };            // 41 words: odd stride, no LDS bank conflicts
 #define G1_DIRECT_BLOCK 64              // one wavefront per workgroup: the dispatcher spreads 1024 of them over the 1024 SIMDs
-static inline uint32_t ilog2_coop(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
 
 // The same stages with FOUR lanes per butterfly (g1_quad.hpp): for launches that would leave most SIMDs empty (at most 16 384 butterflies: up to 8
 // polynomials of 4096 points), where the stage time is the latency of one scalar multiplication on one lane.  The quad shares the digit loop of
@@ -93,8 +90,7 @@ template <bool DIF, bool WNAF, int L> __global__ __launch_bounds__(G1_BLOCK, 2) 
 #undef QMUL
 // the irregular width-5 NAF schedule where every wavefront holds one twiddle (L lanes x (n / 2 / m) batch butterflies per twiddle), else the regular one
 static inline bool g1_quad_wnaf(uint64_t n, uint64_t batch, uint64_t m, int lanes) {
-    static const bool off = [] { const char *e = getenv("KZG_HIP_G1_MUL"); return e && e[0] == 'r'; }();
-    return !off && ((n / 2 / m) * batch * lanes) % 64 == 0;
+    return knobs::g1_mul() != knobs::g1_mul_mode::regular && ((n / 2 / m) * batch * lanes) % 64 == 0;
 }
 // these launches are at most one 256-lane workgroup per CU: 96 KiB of unused dynamic LDS keeps the dispatcher from putting two on one CU (two
 // wavefronts on a SIMD take 1.76x as long as one) while another CU stays empty
@@ -109,7 +105,7 @@ template <bool DIF> static inline void launch_stage_coop(hipStream_t s, int lane
     (void)once;
     const size_t lds = total * lanes <= device_simd_lanes() ? 96 * 1024 : 0;
     const dim3 qg((uint32_t)((lanes * total + G1_BLOCK - 1) / G1_BLOCK));
-    const uint32_t logn = ilog2_coop(n);
+    const uint32_t logn = ilog2(n);
     const bool wn = g1_quad_wnaf(n, batch, m, lanes);
     if (lanes == 4) {
         if (wn) hipLaunchKernelGGL((k_g1_fft_stage_quad<DIF, true, 4>), qg, dim3(G1_BLOCK), lds, s, data, logn, m, roots, wnaf, W, total, batch);

@@ -4,8 +4,11 @@
 #include <stdint.h>
 #include "field.hpp"
 #include "g1.hpp"
+#include "knobs.hpp"
 
 namespace kzg {
+
+inline uint32_t ilog2(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }   // ceil(log2 v)
 
 // ---------------- k_fr.hip ----------------
 // Batched radix-2 FFT over F_r (replaces _fft / InplaceFFT, fft_fr.go:30-105).
@@ -15,6 +18,8 @@ namespace kzg {
 //   tw4096 != nullptr and n == 4096: the radix-4 kernel on lazy limbs with that twiddle file (fr_fft4096.hpp; same direction as roots)
 void launch_fr_fft(hipStream_t s, const fr *in, uint64_t in_stride, uint64_t n_in, fr *out, uint64_t n, uint64_t batch,
                    const fr *roots, uint64_t W, const fr *scale, const uint32_t *tw4096 = nullptr, const fr *roots_l = nullptr);
+// whether launch_fr_fft takes a lazy-limb kernel for `batch` transforms of n points, given the twiddle files and a grid within the limits
+bool fr_fft_lazy_sizes(uint64_t n, uint64_t batch);
 // DASFFTExtension (das_extension.go:7-84), in place on batch rows of n values.
 //   tw2048 != nullptr and n == 2048: the lazy-limb kernel with that twiddle file (fr_das2048.hpp, built from the same two tables)
 void launch_das_ext(hipStream_t s, fr *vals, uint64_t n, uint64_t batch, const fr *expanded, const fr *reversed, uint64_t W,

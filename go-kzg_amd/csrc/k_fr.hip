@@ -6,8 +6,6 @@
 #include "fr_fft4096.hpp"
 #include "fr_das2048.hpp"
 #include "coop_inv.hpp"
-#include <stdlib.h>
-#include <string.h>
 
 namespace kzg {
 
@@ -174,13 +172,19 @@ __global__ void k_fr_fft_stage_glob(fr *data, uint32_t logn, uint64_t m, const f
     v.put(i0, o0); v.put(i1, o1);
 }
 
-static uint32_t ilog2(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
+// The sizes that go through the lazy-limb kernels below unless KZG_HIP_FR_FFT=radix2: 4096 .. 65 536 points at every batch size, shorter transforms (from 4 points)
+// from one workgroup per CU on.  das_ext_rows (capi_core.hip) routes its rows through launch_fr_fft only where this holds.
+bool fr_fft_lazy_sizes(uint64_t n, uint64_t batch) {
+    static_assert(FR_TILE == fr4::N, "launch_fr_fft: whatever is longer than a tile is longer than the radix-4 kernel's transform");
+    if (knobs::fr_fft() == knobs::fr_fft_mode::radix2) return false;
+    return n < fr4::N ? n >= 4 && batch * n >= 256ull * fr4::N : n <= 16 * (uint64_t)fr4::N;
+}
 void launch_fr_fft(hipStream_t s, const fr *in, uint64_t in_stride, uint64_t n_in, fr *out, uint64_t n, uint64_t batch, const fr *roots,
                    uint64_t W, const fr *scale, const uint32_t *tw4096, const fr *roots_l) {
     if (n == 0 || batch == 0) return;
     uint32_t logn = ilog2(n);
-    static const bool radix2_forced = [] { const char *e = getenv("KZG_HIP_FR_FFT"); return e && !strcmp(e, "radix2"); }();   // A/B and test hook
-    if (n == fr4::N && tw4096 && !radix2_forced) {
+    const bool lazy = tw4096 && fr_fft_lazy_sizes(n, batch);
+    if (n == fr4::N && lazy) {
         prof_begin(s, "fr_fft4096");
         if (scale) {
             hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fr_fft4096_r4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, fr4::LDS_BYTES);
@@ -194,8 +198,8 @@ void launch_fr_fft(hipStream_t s, const fr *in, uint64_t in_stride, uint64_t n_i
     }
     // (from one workgroup per CU on: fewer values are quicker on the one-workgroup-per-transform kernel below, whose small workgroups spread over
     // the whole chip -- 2048 transforms of 32 points: 16 workgroups here, 2048 there)
-    static const bool shared_forced = [] { const char *e = getenv("KZG_HIP_FR_FFT"); return e && !strcmp(e, "shared"); }();   // test hook: at every batch size
-    if (n >= 4 && n < fr4::N && (shared_forced || batch * n >= 256ull * fr4::N) && tw4096 && !radix2_forced && (batch + (fr4::N / n) - 1) / (fr4::N / n) <= 0x7fffffffull) {
+    const bool shared_forced = tw4096 && knobs::fr_fft() == knobs::fr_fft_mode::shared;   // test hook: at every batch size
+    if (n >= 4 && n < fr4::N && (shared_forced || lazy) && (batch + (fr4::N / n) - 1) / (fr4::N / n) <= 0x7fffffffull) {
         switch (logn) {
         case 2: launch_fr_fft_small<2>(s, in, in_stride, n_in, out, batch, tw4096, scale); break;
         case 3: launch_fr_fft_small<3>(s, in, in_stride, n_in, out, batch, tw4096, scale); break;
@@ -218,7 +222,7 @@ void launch_fr_fft(hipStream_t s, const fr *in, uint64_t in_stride, uint64_t n_i
         hipLaunchKernelGGL(k_fr_fft_tile<true>, dim3((uint32_t)batch), dim3(T), sh, s, in, in_stride, n_in, out, logn, (uint64_t)1, roots, W, scale);
         return;
     }
-    if (n <= 16 * (uint64_t)fr4::N && tw4096 && roots_l && !radix2_forced && batch * (n / fr4::N) <= 0x7fffffffull && batch <= 65535) {
+    if (lazy && roots_l && batch * (n / fr4::N) <= 0x7fffffffull && batch <= 65535) {
         // 8192 .. 65 536 points: the rows (every R-th element, R = n / 4096) through the LDS-resident 4096-point kernel, then all upper
         // stages in one pass with the row values in registers: two launches, every value read and written twice
         const uint32_t rl = logn - 12;
@@ -335,8 +339,7 @@ void launch_das_ext(hipStream_t s, fr *vals, uint64_t n, uint64_t batch, const f
                     const uint32_t *tw2048) {
     (void)W;
     if (!n || !batch) return;
-    static const bool radix2_forced = [] { const char *e = getenv("KZG_HIP_FR_FFT"); return e && !strcmp(e, "radix2"); }();
-    if (n == das2k::N && tw2048 && !radix2_forced) {
+    if (n == das2k::N && tw2048 && knobs::fr_fft() != knobs::fr_fft_mode::radix2) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_das_ext2048_r4), hipFuncAttributeMaxDynamicSharedMemorySize, das2k::LDS_BYTES);
         prof_begin(s, "das_ext2048");
         hipLaunchKernelGGL(k_das_ext2048_r4, dim3((uint32_t)batch), dim3(das2k::THREADS), das2k::LDS_BYTES, s, vals, tw2048, inv_n);
@@ -655,7 +658,7 @@ void launch_fr_inv_test(hipStream_t s, const fr *in, uint64_t n, fr *out_coop, f
     hipLaunchKernelGGL(k_fr_inv_block, dim3((uint32_t)((n + 1023) / 1024)), dim3(1024), 2048 * sizeof(fr), s, in, n, out_block);
 }
 uint64_t eth_quotient_scratch_elems(uint64_t n, uint64_t batch) {   // elements the caller appends to its quotient buffer for the row-split form (0: not used at this shape)
-    static const bool one_wg = [] { const char *e = getenv("KZG_HIP_ETH_QUOTIENT"); return e && !strcmp(e, "one"); }();   // A/B and test hook: one workgroup per row at every size
+    const bool one_wg = knobs::eth_quotient_one();   // A/B and test hook: one workgroup per row at every size
     const uint64_t S = n / 1024;
     // small batches only: from ~64 rows on the one-workgroup rows fill the chip and their four elements per lane amortise the tree (512 rows: 87 k against 66 k proofs/s)
     if (one_wg || n < 2048 || (n & (n - 1)) != 0 || S > 64 || batch * S > 256) return 0;

@@ -4,7 +4,6 @@
 #define KZG_MULQ_NOINLINE 1   // many mulq call sites in this translation unit: keep the product out of line (I-cache)
 #include "internal.hpp"
 #include "coop_inv.hpp"
-#include <stdlib.h>
 
 namespace kzg {
 
@@ -88,11 +87,10 @@ __global__ void k_g1_bitrev_copy(const g1j *in, uint64_t in_stride, uint64_t n_v
     g1j p = (i < n_valid) ? in[b * in_stride + i] : g1_inf();
     out[b * n + bitrev32g((uint32_t)i, logn)] = p;
 }
-static uint32_t ilog2g(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
 void launch_g1_bitrev_copy(hipStream_t s, const g1j *in, uint64_t in_stride, uint64_t n_valid, g1j *out, uint64_t n, uint64_t batch) {
     uint64_t total = n * batch;
     if (!total) return;
-    hipLaunchKernelGGL(k_g1_bitrev_copy, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, in, in_stride, n_valid, out, ilog2g(n), total);
+    hipLaunchKernelGGL(k_g1_bitrev_copy, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, in, in_stride, n_valid, out, ilog2(n), total);
 }
 
 // One DIT stage with half-size m on bit-reversed data: (x, y) -> (x + w y, x - w y), w = roots[j * W / (2m)].
@@ -157,14 +155,10 @@ template <int MODE, bool PRE = false> __global__ __launch_bounds__(G1_BLOCK, 2) 
 }
 // 4 lanes per butterfly while the quadrupled launch still fits one wavefront per SIMD (65 536 lanes on 256 CUs), 2 while the doubled one does;
 // KZG_HIP_G1_QUAD = 0 / 1 / 2: never / always four / always two
-static int g1_quad_forced() {
-    static const int forced = [] { const char *e = getenv("KZG_HIP_G1_QUAD"); return !e ? -1 : (e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1); }();
-    return forced;
-}
-bool g1_quad_enabled() { return g1_quad_forced() != 0; }
+bool g1_quad_enabled() { return knobs::g1_quad() != 0; }
 // lanes per butterfly of a stage launch: 4, 2 or 1
 static int g1_stage_lanes(uint64_t butterflies) {
-    if (g1_quad_forced() >= 0) return g1_quad_forced() == 0 ? 1 : g1_quad_forced() == 2 ? 2 : 4;
+    if (const int forced = knobs::g1_quad(); forced >= 0) return forced == 0 ? 1 : forced == 2 ? 2 : 4;
     const uint64_t one_round = device_simd_lanes();
     return butterflies * 4 <= one_round ? 4 : butterflies * 2 <= one_round ? 2 : 1;
 }
@@ -226,8 +220,8 @@ void launch_g1_fft_stage_dif(hipStream_t s, g1j *data, uint64_t n, uint64_t batc
         return;
     }
     const dim3 grid((uint32_t)((total + G1_BLOCK - 1) / G1_BLOCK)), block(G1_BLOCK);
-    if (g1_wnaf_rows_pay(n, batch, m)) hipLaunchKernelGGL(k_g1_fft_stage_dif<true>, grid, block, 0, s, data, ilog2g(n), m, roots, wnaf, W, total, batch);
-    else hipLaunchKernelGGL(k_g1_fft_stage_dif<false>, grid, block, 0, s, data, ilog2g(n), m, roots, wnaf, W, total, batch);
+    if (g1_wnaf_rows_pay(n, batch, m)) hipLaunchKernelGGL(k_g1_fft_stage_dif<true>, grid, block, 0, s, data, ilog2(n), m, roots, wnaf, W, total, batch);
+    else hipLaunchKernelGGL(k_g1_fft_stage_dif<false>, grid, block, 0, s, data, ilog2(n), m, roots, wnaf, W, total, batch);
     prof_end(s, "g1_fft_stage");
 }
 // data[b][i] = inf for every odd i: in bit-reversed order these are the coefficients k >= n / 2, i.e. the "h[:n] || inf" padding of
@@ -258,16 +252,16 @@ void launch_g1_fft_stage(hipStream_t s, g1j *data, uint64_t n, uint64_t batch, u
     // (n / 2 / m) * batch consecutive lanes: a multiple of 64 means every wave is uniform; >= 256 means at most a quarter of the
     // waves straddle two twiddles.  Otherwise (late stages of small batches: a single 4096-point transform has 64 different
     // twiddles per wave in its last stage, measured 21 ms against 2.3 ms) the regular signed-window schedule runs instead.
-    static const int forced = [] { const char *e = getenv("KZG_HIP_G1_MUL"); return !e ? -1 : e[0] == 'r' ? 0 : e[0] == 'w' ? 4 : -1; }();
+    const knobs::g1_mul_mode forced = knobs::g1_mul();
     const uint64_t per_twiddle = (n / 2 / m) * batch;
-    const int mode = forced >= 0 ? forced : ((per_twiddle % 64 == 0 || per_twiddle >= 256) ? 4 : 0);
+    const int mode = forced == knobs::g1_mul_mode::regular ? 0 : forced == knobs::g1_mul_mode::wnaf ? 4 : ((per_twiddle % 64 == 0 || per_twiddle >= 256) ? 4 : 0);
     if (const int lanes = g1_stage_lanes(total); lanes > 1) {
         launch_g1_stage_coop_dit(s, lanes, data, n, batch, m, roots, wnaf, W, total);
         prof_end(s, "g1_fft_stage");
         return;
     }
     const dim3 grid((uint32_t)((total + G1_BLOCK - 1) / G1_BLOCK)), block(G1_BLOCK);
-    const uint32_t logn = ilog2g(n);
+    const uint32_t logn = ilog2(n);
     switch (mode) {
     case 4:
         if (g1_wnaf_rows_pay(n, batch, m)) hipLaunchKernelGGL((k_g1_fft_stage<4, true>), grid, block, 0, s, data, logn, m, roots, wnaf, W, total, batch);
@@ -344,7 +338,7 @@ __global__ __launch_bounds__(G1_DIRECT_BLOCK, 2) void k_g1_fft_direct(const g1j 
 // multiplies every output (folded into the last pass).
 void launch_g1_fft_direct(hipStream_t s, const g1j *in, uint64_t in_stride, uint64_t n_valid, g1j *data, g1j *tmp, uint64_t n, uint64_t batch, const fr *roots,
                           uint64_t W, const fr *scale, uint32_t max_logr, int lanes, uint32_t bits_done, uint64_t n_out) {
-    const uint32_t logn = ilog2g(n);
+    const uint32_t logn = ilog2(n);
     if (max_logr < 1 || max_logr > 4) max_logr = 4;
     // bits_done > 0: `in` already holds the result of the passes over the first bits_done bits (launch_fb_direct_pass1); continue from there
     uint32_t bits_left = logn - bits_done;
@@ -364,9 +358,8 @@ void launch_g1_fft_direct(hipStream_t s, const g1j *in, uint64_t in_stride, uint
         if (p + 1 == npass && n_out && n_out < n) while (logU > 0 && (Ns << (logU - 1)) >= n_out) logU--;
         const uint64_t total = (batch * cols) << (logT + logU);
         // as many lanes per term as keep the pass at one wavefront per SIMD (the caller's choice for full passes; pruned ones may take more)
-        static const bool coop_off = [] { const char *e = getenv("KZG_HIP_G1_DIRECT_COOP"); return e && e[0] == '0'; }();
         int L = lanes;
-        if (g1_quad_enabled() && !coop_off && (logT < logR || logU < logR)) L = total * 4 <= device_simd_lanes() ? 4 : total * 2 <= device_simd_lanes() ? 2 : lanes;
+        if (g1_quad_enabled() && knobs::g1_direct_coop() && (logT < logR || logU < logR)) L = total * 4 <= device_simd_lanes() ? 4 : total * 2 <= device_simd_lanes() ? 2 : lanes;
         // 24 KiB of unused dynamic LDS on top of the 10 KiB the kernel needs: at most 4 of these one-wave workgroups fit a CU, so the
         // 1024 of a 4096-point pass land one per SIMD instead of 8 per CU on half of the chip (measured: 2.7 vs 5.4 ms per pass)
         // (only while the pass has at most one wavefront per SIMD: two transforms are 2048 workgroups and want both wave slots)
@@ -442,8 +435,7 @@ __global__ __launch_bounds__(G1_BLOCK, 2) void k_g1_normalize_batched(const g1j 
 }
 void launch_g1_normalize(hipStream_t s, const g1j *in, g1j *out, uint64_t n, bool to_kilic) {
     if (!n) return;
-    static const bool coop_off = [] { const char *e = getenv("KZG_HIP_COOP_INV"); return e && e[0] == '0'; }();   // A/B and test hook: the lane form everywhere
-    if (n < 1024 && !coop_off) {   // small outputs (one commitment, one proof): a wavefront per point, cooperative inversion (in place is fine: a point is read before it is written)
+    if (n < 1024 && knobs::coop_inv()) {   // small outputs (one commitment, one proof): a wavefront per point, cooperative inversion (in place is fine: a point is read before it is written)
         hipLaunchKernelGGL(k_g1_normalize_wave, dim3((uint32_t)n), dim3(64), 0, s, in, out, n, to_kilic ? 1 : 0);
         return;
     }

@@ -425,7 +425,7 @@ void launch_msm(hipStream_t s, const msm_plan &p, const g1a *table, const fr *sc
     uint32_t S = 1;
     while (S < 16 && batch * L.K * S * 2 <= 2 * device_simd_lanes()) S *= 2;
     uint64_t total = batch * L.K * S;
-    static const int seg_mode = [] { const char *e = getenv("KZG_HIP_MSM_SEG"); return e ? atoi(e) : -1; }();   // 0 / 1: never / always the balanced form (A/B runs, tests)
+    const int seg_mode = knobs::msm_seg();   // 0 / 1: never / always the balanced form (A/B runs, tests)
     prof_begin(s, "msm_accumulate");
     // from one full round of resident lanes on (64 MSMs of 4096 points): measured 2.19 vs 2.98 ms at 64, 12.3 vs 17.3 ms at 512; below, the S-lanes-per-bucket
     // form wins (32: 1.89 vs 2.07 ms, 8: 1.14 vs 1.47 ms: its lanes are shorter and a lone MSM is latency-bound)
@@ -440,8 +440,8 @@ void launch_msm(hipStream_t s, const msm_plan &p, const g1a *table, const fr *sc
         hipLaunchKernelGGL(k_msm_accumulate, dim3((uint32_t)((total + MSM_ACC_BLOCK - 1) / MSM_ACC_BLOCK)), dim3(MSM_ACC_BLOCK), 0, s, table, ws, L.per_blob,
                            L.entries_off, L.offsets_off, L.buckets_off, K, S, total);
     prof_end(s, "msm_accumulate");
-    static const int reduce_mode = [] { const char *e = getenv("KZG_HIP_MSM_REDUCE"); return !e ? -1 : !strcmp(e, "chunks") ? 1 : !strcmp(e, "scan") ? 0 : -1; }();   // tests / A/B runs: force a form at any batch size
-    if (reduce_mode == 1 || (reduce_mode < 0 && balanced && batch * p.ngroups * 32 >= device_simd_lanes())) {   // (256 MSMs on a cached set: 37.7 k -> 40.7 k MSM/s, 512: 40.4 k -> 43.4 k; 64 MSMs are faster on the scan: 29.3 k vs 27.6 k)
+    const knobs::msm_reduce_mode reduce_mode = knobs::msm_reduce();   // tests / A/B runs: force a form at any batch size
+    if (reduce_mode == knobs::msm_reduce_mode::chunks || (reduce_mode == knobs::msm_reduce_mode::by_batch && balanced && batch * p.ngroups * 32 >= device_simd_lanes())) {   // (256 MSMs on a cached set: 37.7 k -> 40.7 k MSM/s, 512: 40.4 k -> 43.4 k; 64 MSMs are faster on the scan: 29.3 k vs 27.6 k)
         const uint64_t tg = batch * p.ngroups;
         hipLaunchKernelGGL(k_msm_reduce_chunks, dim3((uint32_t)((tg + 3) / 4)), dim3(MSM_NB), 0, s, ws, L.per_blob, L.buckets_off, L.gsum_off, p.ngroups, tg);
     } else
@@ -1031,8 +1031,7 @@ static uint32_t fb_blocks_per_blob(uint64_t n, uint64_t batch, uint32_t *wsplit 
     // 131072 lanes = 2048 wavefronts = exactly the resident capacity at 2 waves per SIMD: ONE round.  Measured (512 blobs):
     // 131072 lanes 5.7 ms, 262144 lanes (two rounds) 6.4 ms, 98304 / 65536 lanes 10.4 ms.  KZG_HIP_FB_LANES overrides.
     // (thread-safe: coalescer leaders on several host threads get here at once; one value per device)
-    static const uint64_t forced_lanes = [] { const char *e = getenv("KZG_HIP_FB_LANES"); return e ? strtoull(e, nullptr, 10) : 0ull; }();
-    uint64_t lanes = forced_lanes ? forced_lanes : 2 * device_simd_lanes();   // CUs x 4 SIMDs x 2 resident waves x 64 lanes (256 CUs: 131072)
+    uint64_t lanes = knobs::fb_lanes() ? knobs::fb_lanes() : 2 * device_simd_lanes();   // CUs x 4 SIMDs x 2 resident waves x 64 lanes (256 CUs: 131072)
     if (lanes < FB_ACC_BLOCK) lanes = FB_ACC_BLOCK;
     uint64_t target = lanes / FB_ACC_BLOCK;
     uint64_t bpb = target / (batch ? batch : 1);

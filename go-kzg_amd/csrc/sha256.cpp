@@ -1,6 +1,6 @@
 // sha256.cpp -- the compression function behind sha256.hpp: x86 SHA extensions when the CPU has them, a portable loop otherwise
 #include "sha256.hpp"
-#include <cstdlib>
+#include "knobs.hpp"
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
@@ -77,8 +77,7 @@ __attribute__((target("sha,sse4.1,ssse3"))) static inline void sha256_blocks_sha
 static inline bool sha256_use_shani() {
 #if defined(__x86_64__)
     static const bool use = [] {
-        const char *e = getenv("KZG_HIP_SHA256");
-        if (e && !strcmp(e, "portable")) return false;
+        if (knobs::sha256_portable()) return false;
         __builtin_cpu_init();
         return (bool)(__builtin_cpu_supports("sha") && __builtin_cpu_supports("sse4.1") && __builtin_cpu_supports("ssse3"));
     }();
