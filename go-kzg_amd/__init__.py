@@ -122,6 +122,9 @@ def lib():
         "kzg_hip_eth_compute_kzg_proof_batch": (i32, [vp, vp, u64, u64, vp, vp, vp, vp]),
         "kzg_hip_eth_compute_kzg_proof_batch_dev": (i32, [vp, vp, u64, u64, vp, vp, vp, vp, vp]),
         "kzg_hip_eth_compute_aggregate_kzg_proof": (i32, [vp, vp, u64, vp, vp]),
+        "kzg_hip_eth_compute_aggregate_kzg_proof_batch": (i32, [vp, vp, vp, u64, vp, vp, vp]),
+        "kzg_hip_eth_compute_aggregate_kzg_proof_batch_dev": (i32, [vp, vp, vp, u64, vp, vp, vp]),
+        "kzg_hip_test_eth_prove_chunks": (u64, []),
         "kzg_hip_eth_compute_aggregated_poly_and_commitment": (i32, [vp, vp, vp, u64, vp, vp, vp, vp]),
         "kzg_hip_test_sha256": (None, [vp, u64, vp]),
         "kzg_hip_evaluate_poly_in_evaluation_form": (i32, [vp, vp, u64, vp, u32, vp]),
@@ -1094,6 +1097,26 @@ class EthSettings:
                                                                 _p(c48) if intermediates else None, _p(zs) if intermediates else None,
                                                                 _p(ys) if intermediates else None))
         return (out, c48, zs, ys) if intermediates else out
+
+    def compute_aggregate_kzg_proof_batch(self, blobs, counts):
+        """eth.ComputeAggregateKZGProof (eth/eth.go:175-182) over many sidecars in one call: `counts[j]` blobs (0 is valid) of the (sum(counts), n, 32)
+        uint8 blobs belong to sidecar j -> ((sidecars, 48) proofs, (sum(counts), 48) commitments, (sidecars,) uint8 status).  status[j] is 0 where the
+        row's outputs are those of compute_aggregate_kzg_proof on that sidecar alone, byte for byte; else ERR_BAD_BLOB / ERR_BAD_ARG (the status of
+        the lone call), and the row's proof and commitments are zero bytes"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        s, total = counts.shape[0], int(counts.sum(dtype=object)) if counts.shape[0] else 0
+        blobs = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(-1, self.n, 32)
+        if blobs.shape[0] != total:
+            raise KzgError(ERR_LEN_MISMATCH, "sum(counts) blobs")
+        proofs, comm, status = np.zeros((s, 48), dtype=np.uint8), np.zeros((total, 48), dtype=np.uint8), np.zeros(s, dtype=np.uint8)
+        _chk(lib().kzg_hip_eth_compute_aggregate_kzg_proof_batch(self.h, _p(blobs), _p(counts), s, _p(proofs), _p(comm), _p(status)))
+        return proofs, comm, status
+
+    def compute_aggregate_kzg_proof_batch_dev(self, d_blobs, counts, d_proofs, d_commitments, d_status):
+        """the same on DEVICE pointers (integers; blobs 4-byte aligned, d_commitments may be None), enqueued on the handle's stream without a
+        host synchronisation: the caller orders its own streams around the call; `counts` is a host array"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        _chk(lib().kzg_hip_eth_compute_aggregate_kzg_proof_batch_dev(self.h, d_blobs, _p(counts), counts.shape[0], d_proofs, d_commitments, d_status))
 
     def evaluate_polynomial_in_evaluation_form(self, polynomial, x):
         """eth.EvaluatePolynomialInEvaluationForm (eth/helpers.go:207-211)"""

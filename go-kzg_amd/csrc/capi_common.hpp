@@ -132,6 +132,15 @@ struct stream_lease {
             f->pool_cv.wait(lk);
         }
     }
+    // A SECOND stream for a call that already holds one (work that may run beside its main stream).  Never waits: callers that each hold one
+    // stream and wait for another would wait for ever, so `s` stays null when the pool has none to give and the caller does without.
+    stream_lease(kzg_hip_fft *f, std::try_to_lock_t) : fs(f) {
+        std::unique_lock<std::mutex> lk(f->pool_mu);
+        if (!f->pool_idle.empty()) { slot = f->pool_idle.back(); f->pool_idle.pop_back(); s = slot.s; return; }
+        if (f->pool_total >= POOL_MAX) return;
+        if (hipStreamCreateWithFlags(&slot.s, hipStreamNonBlocking) == hipSuccess) { stream_cache_own(slot.s); f->pool_total++; s = slot.s; return; }
+        (void)hipGetLastError(); slot.s = nullptr;
+    }
     // `bytes` of pinned host memory owned by this call, visible to the device at *dev (zero-copy: a kernel that touches every byte exactly
     // once reads its input and writes its output there, no staged hipMemcpy of pageable memory, no device buffer); null if unavailable
     uint8_t *pinned(size_t bytes, void **dev) {
@@ -146,6 +155,7 @@ struct stream_lease {
         return slot.h_pin;
     }
     ~stream_lease() {
+        if (!s) return;                       // a second stream that was not to be had
         if (fallback.owns_lock()) { (void)hipStreamSynchronize(s); return; }
         (void)hipStreamSynchronize(slot.s);   // an early error return may leave kernels in flight that touch the slot's pinned area or stream-ordered temporaries: the next lessee must not see them (free when idle)
         std::lock_guard<std::mutex> lk(fs->pool_mu);

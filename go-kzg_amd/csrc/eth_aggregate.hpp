@@ -39,6 +39,26 @@ KZG_HD void eth_transcript_lane(const uint8_t *blobs, const uint8_t *comms, uint
     z_out = hash_to_bls_field_33(tr, 1);
 }
 
+// The same chain in two halves, for a PROVER: its commitments do not exist yet when its blobs do.  The header is 32 bytes and a blob 32 n
+// bytes with n a power of two >= 2, so the first 32 count n bytes of the message -- the header and all blob bytes but the last 32 -- are
+// count n / 2 whole SHA blocks that no commitment touches.  The blob half hashes them and leaves the eight state words (the initial state
+// for count = 0); the finish half takes the state up again at that block with the last 32 blob bytes and the compressed commitments.
+KZG_HD uint64_t eth_transcript_blob_blocks(uint64_t n, uint64_t count) { return count * n / 2; }
+KZG_HD void eth_transcript_blobs_lane(const uint8_t *blobs, uint64_t n, uint64_t count, uint32_t st[8]) {
+    const eth_transcript_src src{blobs, blobs, n, count};   // (no group of the blob half reaches the commitments)
+    sha256_init(st);
+    sha256_lane_blocks(src, 0, eth_transcript_blob_blocks(n, count), st);
+}
+KZG_HD void eth_transcript_finish_lane(const uint8_t *blobs, const uint8_t *comms, uint64_t n, uint64_t count, const uint32_t st_in[8], fr &r_out, fr &z_out) {
+    const eth_transcript_src src{blobs, comms, n, count};
+    uint32_t tr[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) tr[i] = st_in[i];
+    sha256_lane_resume(src, src.len(), eth_transcript_blob_blocks(n, count), tr);
+    r_out = hash_to_bls_field_33(tr, 0);
+    z_out = hash_to_bls_field_33(tr, 1);
+}
+
 // coefficient i of sum_k r^k blob_k in Horner order from the last blob to the first.  The elements stay PLAIN: the Montgomery product of a
 // plain value and the Montgomery image of r is the plain product, so one product per element and one conversion of the sum at the end
 // give the Montgomery image that bls.PolyLinComb gives.  Returns false when one of the `count` elements is not below r (bls.FrFrom32).

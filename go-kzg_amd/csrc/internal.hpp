@@ -186,6 +186,14 @@ void launch_g2_compress(hipStream_t s, const g2j *in_kilic, uint64_t n, uint8_t 
 // eth.VerifyAggregateKZGProof over a chunk of sidecars: off[j] .. off[j + 1] (sidecars + 1 entries) are sidecar j's blobs and commitments
 // within the chunk's raw bytes (blobs: n x 32 little-endian bytes each; comms: 48 bytes each).  Challenges and powers are Montgomery images.
 void launch_eth_transcripts(hipStream_t s, const uint8_t *blobs, const uint8_t *comms, const uint64_t *off, uint64_t n, uint64_t sidecars, fr *r_out, fr *z_out);
+// the same chain in two halves (the batched prover): st[8 j ..] = the SHA state after the header and all blob bytes of sidecar j but the last 32
+// (no commitment needed); the finish half resumes there with those 32 bytes and the compressed commitments
+void launch_eth_transcript_blobs(hipStream_t s, const uint8_t *blobs, const uint64_t *off, uint64_t n, uint64_t sidecars, uint32_t *st);
+void launch_eth_transcript_finish(hipStream_t s, const uint8_t *blobs, const uint8_t *comms, const uint64_t *off, uint64_t n, uint64_t sidecars, const uint32_t *st,
+                                  fr *r_out, fr *z_out);
+// status[j] = code_blob where agg_status[j], else code_z where z_in_domain[j], else 0; zero bytes over the proof and the commitments (may be null) of a failed row
+void launch_eth_prove_finish(hipStream_t s, const uint8_t *agg_status, const uint32_t *z_in_domain, const uint64_t *off, uint64_t sidecars, uint8_t code_blob,
+                             uint8_t code_z, uint8_t *proofs48, uint8_t *comms48, uint8_t *status);
 // agg[j][i] = sum_k r_j^k blob_(j,k)[i]; status[j] = 2 where an element of the sidecar is not below r (status is otherwise left alone)
 void launch_eth_agg_poly(hipStream_t s, const uint8_t *blobs, const uint64_t *off, const fr *r, uint64_t n, uint64_t sidecars, fr *agg, uint8_t *status);
 void launch_eth_powers(hipStream_t s, const fr *r, const uint64_t *off, uint64_t sidecars, fr *pow);   // pow[off[j] + k] = r_j^k

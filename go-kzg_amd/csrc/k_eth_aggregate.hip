@@ -30,6 +30,63 @@ void launch_eth_transcripts(hipStream_t s, const uint8_t *blobs, const uint8_t *
     prof_end(s, "eth_transcripts");
 }
 
+// The chain in two halves, for the batched block PROVER (capi_eth_prove.hip): its commitments are computed on the device from the same
+// blobs, so all of a chain but its last 48 count + 32 bytes is hashed beside the table walk.  One lane per sidecar as above; st is eight
+// words per sidecar.
+__global__ __launch_bounds__(TRANSCRIPT_BLOCK) void k_eth_transcript_blobs(const uint8_t *blobs, const uint64_t *off, uint64_t n, uint64_t sidecars, uint32_t *st) {
+    const uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (j >= sidecars) return;
+    const uint64_t o = off[j], count = off[j + 1] - o;
+    uint32_t s[8];
+    eth_transcript_blobs_lane(blobs + o * n * 32, n, count, s);
+#pragma unroll
+    for (int i = 0; i < 8; i++) st[8 * j + i] = s[i];
+}
+void launch_eth_transcript_blobs(hipStream_t s, const uint8_t *blobs, const uint64_t *off, uint64_t n, uint64_t sidecars, uint32_t *st) {
+    if (!sidecars) return;
+    prof_begin(s, "eth_transcript_blobs");
+    hipLaunchKernelGGL(k_eth_transcript_blobs, grid_for(sidecars, TRANSCRIPT_BLOCK), dim3(TRANSCRIPT_BLOCK), 0, s, blobs, off, n, sidecars, st);
+    prof_end(s, "eth_transcript_blobs");
+}
+__global__ __launch_bounds__(TRANSCRIPT_BLOCK) void k_eth_transcript_finish(const uint8_t *blobs, const uint8_t *comms, const uint64_t *off, uint64_t n, uint64_t sidecars,
+                                                                            const uint32_t *st, fr *r_out, fr *z_out) {
+    const uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (j >= sidecars) return;
+    const uint64_t o = off[j], count = off[j + 1] - o;
+    uint32_t s[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) s[i] = st[8 * j + i];
+    fr r, z;
+    eth_transcript_finish_lane(blobs + o * n * 32, comms + o * 48, n, count, s, r, z);
+    r_out[j] = r; z_out[j] = z;
+}
+void launch_eth_transcript_finish(hipStream_t s, const uint8_t *blobs, const uint8_t *comms, const uint64_t *off, uint64_t n, uint64_t sidecars, const uint32_t *st,
+                                  fr *r_out, fr *z_out) {
+    if (!sidecars) return;
+    prof_begin(s, "eth_transcript_finish");
+    hipLaunchKernelGGL(k_eth_transcript_finish, grid_for(sidecars, TRANSCRIPT_BLOCK), dim3(TRANSCRIPT_BLOCK), 0, s, blobs, comms, off, n, sidecars, st, r_out, z_out);
+    prof_end(s, "eth_transcript_finish");
+}
+// the prover's last step, one lane per sidecar: the row's status byte -- code_blob where k_eth_agg_poly found an element >= r (it wins, the
+// lone call's order), code_z where the evaluation challenge lies in the domain, else 0 -- and zero bytes over the proof and the commitments
+// of a failed row (byte stores: a caller's buffers may have any alignment; failed rows are rare).  comms48 may be null.
+__global__ __launch_bounds__(AGG_BLOCK) void k_eth_prove_finish(const uint8_t *agg_status, const uint32_t *z_in_domain, const uint64_t *off, uint64_t sidecars,
+                                                                uint8_t code_blob, uint8_t code_z, uint8_t *proofs48, uint8_t *comms48, uint8_t *status) {
+    const uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (j >= sidecars) return;
+    const uint8_t code = agg_status[j] ? code_blob : z_in_domain[j] ? code_z : 0;
+    status[j] = code;
+    if (!code) return;
+    for (uint32_t i = 0; i < 48; i++) proofs48[48 * j + i] = 0;
+    if (comms48) for (uint64_t i = 48 * off[j]; i < 48 * off[j + 1]; i++) comms48[i] = 0;
+}
+void launch_eth_prove_finish(hipStream_t s, const uint8_t *agg_status, const uint32_t *z_in_domain, const uint64_t *off, uint64_t sidecars, uint8_t code_blob,
+                             uint8_t code_z, uint8_t *proofs48, uint8_t *comms48, uint8_t *status) {
+    if (!sidecars) return;
+    hipLaunchKernelGGL(k_eth_prove_finish, grid_for(sidecars, AGG_BLOCK), dim3(AGG_BLOCK), 0, s, agg_status, z_in_domain, off, sidecars, code_blob, code_z, proofs48, comms48,
+                       status);
+}
+
 // lane (sidecar j, coefficient i): the aggregated polynomial's coefficient from the blobs' bytes; an element >= r marks the SIDECAR (status 2,
 // the same byte from every lane that finds one)
 __global__ __launch_bounds__(AGG_BLOCK) void k_eth_agg_poly(const uint8_t *blobs, const uint64_t *off, const fr *r, uint64_t n, uint64_t sidecars, fr *agg, uint8_t *status) {

@@ -73,6 +73,7 @@ KZG_KNOB_ONCE(bool, coop_inv, "KZG_HIP_COOP_INV", !starts(e, '0'))              
 KZG_KNOB_ONCE(bool, fk20_pass1, "KZG_HIP_FK20_PASS1", !starts(e, '0'))                  // off: Toeplitz stage and first direct pass of a lone polynomial as separate kernels
 KZG_KNOB_ONCE(bool, fk20_fuse, "KZG_HIP_FK20_FUSE", !starts(e, '0'))                    // off: the unfused FK20 pipeline (tests compare both)
 KZG_KNOB_ONCE(bool, fk20_pad, "KZG_HIP_FK20_PAD", !starts(e, '0'))                      // off: ragged FK20 batches are not padded
+KZG_KNOB_PER_CALL(bool, eth_prove_overlap, "KZG_HIP_ETH_PROVE_OVERLAP", !starts(e, '0'))     // off: the batched aggregate prover hashes the blob half of its transcripts on the main stream, not beside the table walk (A/B runs, tests)
 // default off, on when set at all (the empty string included)
 KZG_KNOB_ONCE(bool, coalesce_trace, "KZG_HIP_COALESCE_TRACE", e != nullptr)             // phase times of every coalesced commitment batch on stderr (adds two synchronisations)
 KZG_KNOB_PER_CALL(bool, coalesce_stats, "KZG_HIP_COALESCE_STATS", e != nullptr)         // a coalescer prints its statistics on stderr when it is destroyed
@@ -88,7 +89,7 @@ KZG_KNOB_ONCE(zero_poly_mode, zero_poly_once, "KZG_HIP_ZERO_POLY", zero_poly_of(
 KZG_KNOB_PER_CALL(zero_poly_mode, zero_poly_per_call, "KZG_HIP_ZERO_POLY", zero_poly_of(e))                                                 // the batch calls (a measurement switches within one process)
 KZG_KNOB_ONCE(msm_reduce_mode, msm_reduce, "KZG_HIP_MSM_REDUCE", is(e, "chunks") ? msm_reduce_mode::chunks : is(e, "scan") ? msm_reduce_mode::scan : msm_reduce_mode::by_batch)   // bucket MSM: force a reduce form (A/B runs, tests)
 KZG_KNOB_ONCE(int, msm_seg, "KZG_HIP_MSM_SEG", e ? atoi(e) : -1)                                                                            // bucket MSM: 0 / 1 never / always the balanced accumulate; any other number: by batch
-KZG_KNOB_PER_CALL(transcript_mode, eth_transcript, "KZG_HIP_ETH_TRANSCRIPT", is(e, "host") ? transcript_mode::host : is(e, "device") ? transcript_mode::device : transcript_mode::by_count)   // where the aggregate verifier hashes
+KZG_KNOB_PER_CALL(transcript_mode, eth_transcript, "KZG_HIP_ETH_TRANSCRIPT", is(e, "host") ? transcript_mode::host : is(e, "device") ? transcript_mode::device : transcript_mode::by_count)   // where the aggregate verifier and the batched aggregate prover hash
 KZG_KNOB_PER_CALL(int, multi_fft, "KZG_HIP_MULTI_FFT", !e ? -1 : is(e, "sharded") ? 1 : 0)                                                   // -1 the handle's policy; "sharded" 1; ANY other value gathers (0)
 KZG_KNOB_PER_HANDLE(transport_mode, multi_transport, "KZG_HIP_MULTI_TRANSPORT", !e ? transport_mode::by_devices : is(e, "rccl") ? transport_mode::rccl : is(e, "host") ? transport_mode::host : transport_mode::peer)   // any other value: peer copies, RCCL is not bound
 KZG_KNOB_PER_HANDLE(unsigned, multi_fault, "KZG_HIP_MULTI_FAULT", multi_fault_of(e))                                                        // tests: a comma-separated list of legs of the exchange that fail, FAULT_* above
@@ -99,6 +100,7 @@ KZG_KNOB_ONCE(uint32_t, lincomb_promote_after, "KZG_HIP_LINCOMB_PROMOTE_AFTER", 
 KZG_KNOB_ONCE(uint64_t, fb_lanes, "KZG_HIP_FB_LANES", e ? strtoull(e, nullptr, 10) : 0ull)                                                  // lanes of one table-walk launch; 0: two resident waves per SIMD
 KZG_KNOB_ONCE(uint64_t, eth_stage_rows, "KZG_HIP_ETH_STAGE_ROWS", e ? (uint64_t)atol(e) : 0ull)                                             // coalesced eth proof batches of up to this many rows are copied to HBM first (A/B runs, tests)
 KZG_KNOB_PER_CALL(double, eth_verify_chunk_mb, "KZG_HIP_ETH_VERIFY_CHUNK_MB", positive_or(e, 4096.0))                                      // blob bytes per chunk of the aggregate verifier; fractions allowed, <= 0 is the default
+KZG_KNOB_PER_CALL(double, eth_prove_chunk_mb, "KZG_HIP_ETH_PROVE_CHUNK_MB", positive_or(e, 4096.0))                                        // device bytes per chunk of the batched aggregate prover (twice a sidecar's blob bytes + two rows); likewise
 KZG_KNOB_PER_CALL(double, recover_chunk_mb, "KZG_HIP_RECOVER_CHUNK_MB", positive_or(e, 2048.0))                                            // device memory per chunk of the batched recovery; likewise
 KZG_KNOB_PER_CALL(opt_gb, fb_budget_gb, "KZG_HIP_FB_BUDGET_GB", (opt_gb{e != nullptr, e ? atof(e) : 0.0}))                                  // commitment tables; not clamped (negative: no table fits)
 KZG_KNOB_PER_CALL(opt_gb, points_fb_budget_gb, "KZG_HIP_POINTS_FB_BUDGET_GB", (opt_gb{e != nullptr, e ? atof(e) : 0.0}))                    // tables of cached point sets

@@ -52,6 +52,9 @@ void kzg_hip_test_sha256(const void *data, uint64_t len, void *out32);
  * hashToBLSField's reduction of `rows` given 32-byte digests (read as little-endian integers, reduced mod r; out_fr: rows Fr) */
 int kzg_hip_test_sha256_lanes(kzg_hip_fft *fs, const void *data, const uint64_t *offsets, const uint64_t *lens, uint64_t rows, void *out32);
 int kzg_hip_test_hash_to_bls_field_lanes(kzg_hip_fft *fs, const void *digests32, uint64_t rows, void *out_fr);
+/* test hook of the batched block prover (capi_eth_prove.hip): how many chunks of whole sidecars the calling thread's last successful
+ * kzg_hip_eth_compute_aggregate_kzg_proof_batch[_dev] ran as (KZG_HIP_ETH_PROVE_CHUNK_MB) */
+uint64_t kzg_hip_test_eth_prove_chunks(void);
 
 /* test hook of the pairing (k_pairing.hip): out_fp12[i] = e(g1[i], g2[i]) raised to 3 (p^12 - 1) / r (the exponent of pairing.hpp's final
  * exponentiation), 12 F_p elements of 48 bytes each in STANDARD form, order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1; G1 / G2 Kilic images in */

@@ -44,16 +44,21 @@ KZG_HD void sha256_compress(uint32_t st[8], uint32_t w[16]) {
     }
     st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
 }
-// digest (eight big-endian words, the SHA's own state) of the `len` bytes of src
-template <class Src> KZG_HD void sha256_lane(const Src &src, uint64_t len, uint32_t st[8]) {
-    sha256_init(st);
+// the whole blocks first .. last - 1 of src into the state st (in and out): a chain cut at a block boundary and taken up again later
+template <class Src> KZG_HD void sha256_lane_blocks(const Src &src, uint64_t first, uint64_t last, uint32_t st[8]) {
     uint32_t w[16];
-    const uint64_t full = len / 64;
-    for (uint64_t b = 0; b < full; b++) {
+    for (uint64_t b = first; b < last; b++) {
 #pragma unroll
         for (int q = 0; q < 4; q++) src.load16(64 * b + 16 * q, w + 4 * q);
         sha256_compress(st, w);
     }
+}
+// the resumable form: st holds the state after the first `first` blocks of the `len` bytes of src (sha256_init's for first = 0); hashes the
+// rest and leaves the digest (eight big-endian words, the SHA's own state) in st.  first <= len / 64.
+template <class Src> KZG_HD void sha256_lane_resume(const Src &src, uint64_t len, uint64_t first, uint32_t st[8]) {
+    uint32_t w[16];
+    const uint64_t full = len / 64;
+    sha256_lane_blocks(src, first, full, st);
     // the last block(s): the rest of the message, 0x80, zeros, the length in bits as 64 big-endian bits; two blocks when fewer than 9 bytes are free
     const uint32_t rem = (uint32_t)(len & 63);
     const uint64_t base = 64 * full;
@@ -82,6 +87,11 @@ template <class Src> KZG_HD void sha256_lane(const Src &src, uint64_t len, uint3
     }
     w[14] = (uint32_t)(bits >> 32); w[15] = (uint32_t)bits;
     sha256_compress(st, w);
+}
+// digest of the `len` bytes of src
+template <class Src> KZG_HD void sha256_lane(const Src &src, uint64_t len, uint32_t st[8]) {
+    sha256_init(st);
+    sha256_lane_resume(src, len, 0, st);
 }
 
 // a plain byte buffer as a message source (any alignment)

@@ -170,6 +170,57 @@ func ComputeAggregateKZGProof(blobs BlobSequence) (KZGProof, error) {
 	}
 }
 
+// ComputeAggregateKZGProofBatch: (proofs[j], commitments[j], errs[j]) = ComputeAggregateKZGProof(blobs[j]) with the commitments of its blobs
+// (eth/eth.go:175-182, eth/helpers.go:166-169) for many blocks in one device call.  A block without blobs is valid input; a block with an error
+// keeps the zero proof and no commitments, and changes nothing in the others.
+func ComputeAggregateKZGProofBatch(blobs []BlobSequence) ([]KZGProof, [][]KZGCommitment, []error) {
+	s := len(blobs)
+	proofs, comms, errs := make([]KZGProof, s), make([][]KZGCommitment, s), make([]error, s)
+	if s == 0 {
+		return proofs, comms, errs
+	}
+	counts := make([]uint64, s)
+	total := 0
+	for j := range blobs {
+		counts[j] = uint64(blobs[j].Len())
+		total += blobs[j].Len()
+	}
+	flat := make([]Blob, total)
+	at := 0
+	for j := range blobs {
+		for i := 0; i < blobs[j].Len(); i++ {
+			flat[at] = blobs[j].At(i)
+			at++
+		}
+	}
+	all := make([]KZGCommitment, total)
+	var bp, cp unsafe.Pointer
+	if total > 0 {
+		bp, cp = unsafe.Pointer(&flat[0]), unsafe.Pointer(&all[0])
+	}
+	status := make([]uint8, s)
+	if st := C.kzg_hip_eth_compute_aggregate_kzg_proof_batch(hipEth, bp, (*C.uint64_t)(unsafe.Pointer(&counts[0])), C.uint64_t(s), unsafe.Pointer(&proofs[0]), cp,
+		(*C.uint8_t)(unsafe.Pointer(&status[0]))); st != C.KZG_HIP_OK {
+		panic(fmt.Sprintf("kzg_hip: eth_compute_aggregate_kzg_proof_batch: status %d", int(st)))
+	}
+	at = 0
+	for j, st := range status {
+		n := int(counts[j])
+		switch st {
+		case C.KZG_HIP_OK:
+			comms[j] = all[at : at+n : at+n]
+		case C.KZG_HIP_ERR_BAD_BLOB:
+			errs[j] = errors.New("could not convert blobs to polynomials")
+		case C.KZG_HIP_ERR_BAD_ARG:
+			errs[j] = errors.New("invalid z challenge")
+		default:
+			panic(fmt.Sprintf("kzg_hip: ComputeAggregateKZGProofBatch: row status %d", int(st)))
+		}
+		at += n
+	}
+	return proofs, comms, errs
+}
+
 // VerifyAggregateKZGProof replaces eth/eth.go:155-172: aggregation and evaluation on the device, the pairing
 // (VerifyKZGProofFromPoints, eth/helpers.go:55-68) here as before.
 func VerifyAggregateKZGProof(blobs BlobSequence, expectedKZGCommitments KZGCommitmentSequence, kzgAggregatedProof KZGProof) (bool, error) {

@@ -294,6 +294,24 @@ int kzg_hip_eth_verify_kzg_proof_batch(kzg_hip_eth *eth, const void *commitments
 int kzg_hip_eth_verify_aggregate_kzg_proof_batch(kzg_hip_eth *eth, const void *blobs_le32, const uint64_t *blob_counts, const void *commitments48,
                                                  const void *proofs48, uint64_t sidecars, uint8_t *result,
                                                  void *out_agg_commitments48, void *out_zs_fr, void *out_ys_fr);
+/* eth.ComputeAggregateKZGProof (eth/eth.go:175-181) over `sidecars` blocks in one call, the prover-side twin of the call above.  blob_counts[j] blobs
+ * belong to block j (0 is valid: its proof is the compressed point at infinity); blobs_le32 holds all blobs in block order.  Writes one 48-byte proof per
+ * block and, unless out_commitments48 is NULL, the 48-byte commitment of every blob in the same order as the blobs.  status[j] is 0 when block j's
+ * outputs are written, else the status kzg_hip_eth_compute_aggregate_kzg_proof returns for that block alone: KZG_HIP_ERR_BAD_BLOB (a field element >= r)
+ * or KZG_HIP_ERR_BAD_ARG ("invalid z challenge": the evaluation challenge lies in the domain); such a block gets zero bytes as its proof and as each
+ * of its commitments and changes nothing in its neighbours.  Proof and commitments of a block with status 0 are byte for byte those of the lone call.
+ * sidecars == 0 is KZG_HIP_OK and touches nothing; NULL blob_counts / out_proofs48 / status (or blobs_le32 with a blob to read) KZG_HIP_ERR_BAD_ARG;
+ * KZG_HIP_ERR_TOO_WIDE when the sum of blob_counts or a byte offset overflows.  The work runs per chunk of whole sidecars (KZG_HIP_ETH_PROVE_CHUNK_MB
+ * of device memory, default 4096: a block costs twice its blob bytes plus 64 n bytes; a larger block forms a chunk by itself) on a stream of the
+ * handle's pool, so concurrent callers are not serialised by the handle's own stream.  The Fiat-Shamir transcripts are hashed on the device from
+ * KZG_HIP_ETH_TRANSCRIPT's threshold on (one lane per block, the part that needs no commitment beside the table walk), below it on the calling
+ * thread while the device commits; both return identical bytes. */
+int kzg_hip_eth_compute_aggregate_kzg_proof_batch(kzg_hip_eth *eth, const void *blobs_le32, const uint64_t *blob_counts, uint64_t sidecars, void *out_proofs48,
+                                                  void *out_commitments48, uint8_t *status);
+/* The same with the blobs (4-byte aligned), proofs, commitments and status bytes DEVICE-resident: enqueued on the handle's stream, no host
+ * synchronisation (but for the first call's table build), transcripts always on the device.  blob_counts stays a HOST array: it sizes the launches. */
+int kzg_hip_eth_compute_aggregate_kzg_proof_batch_dev(kzg_hip_eth *eth, const void *d_blobs_le32, const uint64_t *blob_counts, uint64_t sidecars,
+                                                      void *d_out_proofs48, void *d_out_commitments48, uint8_t *d_status);
 /* ---- erasure recovery ----
  * FFTSettings.ZeroPolyViaMultiplication (zero_poly.go:116-217): vanishing polynomial of the missing indices of a size-`length`
  * domain; writes `length` evaluations and `length` coefficients (zero-padded).  No missing index -> all zeros (:117-119). */

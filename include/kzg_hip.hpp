@@ -405,6 +405,25 @@ class Settings {
         if (commitments) *commitments = comm;
         return out;
     }
+    // eth.ComputeAggregateKZGProof over many sidecars in one device call: one proof per sidecar, status[j] = 0 or the lone call's status
+    // (KZG_HIP_ERR_BAD_BLOB / KZG_HIP_ERR_BAD_ARG; the row's proof and commitments are then zero bytes); commitments: one row per sidecar
+    std::vector<Bytes48> ComputeAggregateKZGProofBatch(const std::vector<std::vector<Blob>> &blobs, std::vector<uint8_t> &status,
+                                                       std::vector<std::vector<Bytes48>> *commitments = nullptr) const {
+        std::vector<uint8_t> flat; std::vector<uint64_t> counts;
+        for (const auto &sc : blobs) {
+            counts.push_back(sc.size());
+            for (const auto &b : sc) { if (b.size() != n_ * 32) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "blob size"); flat.insert(flat.end(), b.begin(), b.end()); }
+        }
+        std::vector<Bytes48> out(blobs.size()), comm(flat.size() / (n_ * 32));
+        status.assign(blobs.size(), 0);
+        detail::must(kzg_hip_eth_compute_aggregate_kzg_proof_batch(h_, flat.data(), counts.data(), blobs.size(), out.data(), comm.data(), status.data()));
+        if (commitments) {
+            commitments->clear();
+            size_t at = 0;
+            for (uint64_t c : counts) { commitments->emplace_back(comm.begin() + at, comm.begin() + at + c); at += c; }
+        }
+        return out;
+    }
 
   private:
     kzg_hip_eth *h_ = nullptr; uint64_t n_;
