@@ -102,6 +102,11 @@ def lib():
         "kzg_hip_check_proof_multi_batch": (i32, [vp, vp, vp, vp, vp, u64, u64, vp]),
         "kzg_hip_eth_set_setup_g2": (i32, [vp, vp, u64]), "kzg_hip_eth_verify_kzg_proof_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "kzg_hip_eth_verify_aggregate_kzg_proof_batch": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "kzg_hip_eth_kzg_to_versioned_hash_batch": (i32, [vp, vp, u64, vp]), "kzg_hip_eth_kzg_to_versioned_hash_batch_dev": (i32, [vp, vp, u64, vp]),
+        "kzg_hip_eth_point_evaluation_precompile_batch": (i32, [vp, vp, u64, vp]),
+        "kzg_hip_eth_point_evaluation_precompile_batch_dev": (i32, [vp, vp, u64, vp]),
+        "kzg_hip_eth_precompile_return_value": (i32, [vp, vp]),
+        "kzg_hip_eth_verify_kzg_commitments_against_transactions_batch": (i32, [vp, vp, vp, vp, vp, vp, u64, vp]),
         "kzg_hip_test_sha256_lanes": (i32, [vp, vp, vp, vp, u64, vp]), "kzg_hip_test_hash_to_bls_field_lanes": (i32, [vp, vp, u64, vp]),
         "kzg_hip_pairing_test": (i32, [vp, vp, vp, u64, vp]),
         "kzg_hip_toeplitz_part2": (i32, [vp, vp, vp, u64, vp]), "kzg_hip_toeplitz_part3": (i32, [vp, vp, u64, vp]),
@@ -1077,6 +1082,74 @@ class EthSettings:
             raise KzgError(ERR_LEN_MISMATCH, "one commitment, z, y and proof per check")
         out = np.zeros(n, dtype=np.uint8)
         _chk(lib().kzg_hip_eth_verify_kzg_proof_batch(self.h, _p(c), _p(zs), _p(ys), _p(pi), n, _p(out)))
+        return out
+
+    def kzg_to_versioned_hash_batch(self, commitments):
+        """eth.KZGToVersionedHash (eth/eth.go:137-141) over (count, 48) uint8 commitments (any bytes: nothing is decoded) -> (count, 32) uint8"""
+        c = np.ascontiguousarray(commitments, dtype=np.uint8).reshape(-1, 48)
+        out = np.zeros((c.shape[0], 32), dtype=np.uint8)
+        _chk(lib().kzg_hip_eth_kzg_to_versioned_hash_batch(self.h, _p(c), c.shape[0], _p(out)))
+        return out
+
+    def kzg_to_versioned_hash_batch_dev(self, d_commitments, count, d_out):
+        """the same on DEVICE pointers (integers; d_out 4-byte aligned), enqueued on the handle's stream without a host synchronisation"""
+        _chk(lib().kzg_hip_eth_kzg_to_versioned_hash_batch_dev(self.h, d_commitments, count, d_out))
+
+    PRECOMPILE_INPUT_LENGTH = 192
+    CODE_INVALID_INPUT_LENGTH = 9   # of this binding only: the C ABI takes rows of 192 bytes and has no such code
+
+    def point_evaluation_precompile_batch(self, inputs):
+        """eth.PointEvaluationPrecompile (eth/eth.go:76-110) over a (count, 192) uint8 array or a list of byte strings (versioned hash 32 | z 32 LE |
+        y 32 LE | commitment 48 | proof 48) -> uint8 codes: 1 valid (the reference returns precompile_return_value()), 0 "invalid kzg proof",
+        4 "mismatched versioned hash", 2 z or y not below r, 3 commitment or proof not a valid G1 encoding, in the reference's order of checks
+        (4, then 2, then 3).  A byte string of another length gets CODE_INVALID_INPUT_LENGTH = 9 ("invalid input length") here in the binding,
+        without going to the device; the C ABI has no such code."""
+        if isinstance(inputs, np.ndarray):
+            rows = np.ascontiguousarray(inputs, dtype=np.uint8).reshape(-1, 192)
+            out = np.zeros(rows.shape[0], dtype=np.uint8)
+            _chk(lib().kzg_hip_eth_point_evaluation_precompile_batch(self.h, _p(rows), rows.shape[0], _p(out)))
+            return out
+        inputs = [bytes(b) for b in inputs]
+        out = np.full(len(inputs), self.CODE_INVALID_INPUT_LENGTH, dtype=np.uint8)
+        good = [i for i, b in enumerate(inputs) if len(b) == 192]
+        if good:
+            out[good] = self.point_evaluation_precompile_batch(np.frombuffer(b"".join(inputs[i] for i in good), dtype=np.uint8))
+        elif not inputs:
+            self.point_evaluation_precompile_batch(np.zeros((0, 192), dtype=np.uint8))   # (the empty call still needs the G2 setup)
+        return out
+
+    def point_evaluation_precompile_batch_dev(self, d_inputs, count, d_result):
+        """the same on DEVICE pointers (integers), enqueued on the handle's stream without a host synchronisation"""
+        _chk(lib().kzg_hip_eth_point_evaluation_precompile_batch_dev(self.h, d_inputs, count, d_result))
+
+    def precompile_return_value(self):
+        """precompileReturnValue (eth/globals.go:70-71): n and r as 32 big-endian bytes each"""
+        out = C.create_string_buffer(64)
+        _chk(lib().kzg_hip_eth_precompile_return_value(self.h, out))
+        return out.raw
+
+    def verify_kzg_commitments_against_transactions_batch(self, blocks, commitments):
+        """eth.VerifyKZGCommitmentsAgainstTransactions (eth/eth.go:261-282) over many blocks: blocks[j] is the list of block j's serialized
+        transactions (byte strings), commitments[j] its (k, 48) uint8 commitments (or a list of 48-byte strings) -> uint8 codes: 1 valid, 6 / 7 / 8
+        the block's first malformed blob transaction (too short, also an empty transaction; offset out of bounds; trailing data no multiple of 32),
+        5 the number of versioned hashes differs from the number of commitments, 4 a versioned hash does not match its commitment"""
+        if len(blocks) != len(commitments):
+            raise KzgError(ERR_LEN_MISMATCH, "one list of commitments per block")
+        txs = [bytes(t) for b in blocks for t in b]
+        offsets = np.zeros(len(txs) + 1, dtype=np.uint64)
+        if txs:
+            offsets[1:] = np.cumsum([len(t) for t in txs], dtype=np.uint64)
+        data = np.frombuffer(b"".join(txs) or bytes(1), dtype=np.uint8)
+        tx_counts = np.array([len(b) for b in blocks], dtype=np.uint64)
+        comm = [np.frombuffer(b"".join(bytes(x) for x in c), dtype=np.uint8) if isinstance(c, (list, tuple)) else np.ascontiguousarray(c, dtype=np.uint8).reshape(-1)
+                for c in commitments]
+        if any(c.shape[0] % 48 for c in comm):
+            raise KzgError(ERR_LEN_MISMATCH, "commitments of 48 bytes")
+        comm_counts = np.array([c.shape[0] // 48 for c in comm], dtype=np.uint64)
+        flat = np.ascontiguousarray(np.concatenate(comm + [np.zeros(48, dtype=np.uint8)]))
+        out = np.zeros(len(blocks), dtype=np.uint8)
+        _chk(lib().kzg_hip_eth_verify_kzg_commitments_against_transactions_batch(self.h, _p(data), _p(offsets), _p(tx_counts), _p(flat), _p(comm_counts), len(blocks),
+                                                                                 _p(out)))
         return out
 
     def verify_aggregate_kzg_proof_batch(self, blobs, counts, commitments, proofs, intermediates=False):

@@ -250,6 +250,9 @@ struct kzg_hip_eth {
     std::unique_ptr<coalescer> co_proof;  // concurrent ComputeKZGProof calls (eth/helpers.go:179-203)
     std::shared_ptr<g2_state> g2;         // kzg_hip_eth_set_setup_g2: kzgSetupG2 and its prepared points (capi_verify.hip)
     std::mutex g2_mu;
+    // states that kernels queued by a _dev call may still read, each with an event recorded behind those kernels on the handle's stream
+    // (eth_g2_hold_on_stream / eth_g2_release_passed, capi_verify.hip); under g2_mu
+    std::vector<std::pair<hipEvent_t, std::shared_ptr<g2_state>>> g2_queued;
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -279,6 +282,14 @@ bool coalescing_enabled();   // capi_kzg.hip
 coalescer *get_coalescer(kzg_hip_fft *fs, std::unique_ptr<coalescer> &slot, size_t in_row, size_t out_row, int callers_per_batch = 0);   // capi_kzg.hip
 int coalesce_upload_rows(coalesce_buf &b, uint64_t batch, size_t in_row_bytes, uint64_t n_max, fr *d_rows, uint64_t *d_meta);   // capi_kzg.hip
 int proof_single_rows(kzg_hip_kzg *ks, hipStream_t s, const fr *d_poly, uint64_t n, uint64_t batch, const uint64_t *d_x_u64, uint64_t x_stride, g1j *d_out);   // capi_kzg.hip
+// the prepared [1]G2 and kzgSetupG2[1] of an eth handle; `hold` keeps them alive for the caller's whole check.  KZG_HIP_ERR_BAD_ARG before kzg_hip_eth_set_setup_g2
+int eth_g2_lines(kzg_hip_eth *eth, std::shared_ptr<g2_state> &hold, const g2_prepared **gen, const g2_prepared **s1);   // capi_verify.hip
+// For a call that returns while kernels that read `hold` are still queued on the handle's stream s (the caller holds the handle's mutex): the
+// handle keeps `hold` until an event recorded here has completed.  A state is only ever let go on an ordinary host thread, never in a stream
+// callback (~g2_state calls hipFree, which waits for the device's streams): by eth_g2_release_passed, which the next such call, the next
+// kzg_hip_eth_set_setup_g2 and kzg_hip_eth_settings_free run.  If the event cannot be recorded the stream is drained before the error returns.
+int eth_g2_hold_on_stream(kzg_hip_eth *eth, hipStream_t s, const std::shared_ptr<g2_state> &hold);   // capi_verify.hip
+void eth_g2_release_passed(kzg_hip_eth *eth, bool all = false);   // capi_verify.hip; all: the device has drained (kzg_hip_eth_settings_free)
 int fk20_hext(fk20_core *c, hipStream_t s, const fr *d_poly, uint64_t poly_stride, uint64_t n, uint64_t batch, uint64_t j0, uint64_t cnt, g1j *d_hext);   // capi_fk20.hip
 int fk20_finish(fk20_core *c, hipStream_t s, const g1j *d_hext, uint64_t batch, int da, int bit_reverse, g1j *d_out);   // capi_fk20.hip
 int fk20_run_dev(fk20_core *c, hipStream_t s, const fr *d_poly, uint64_t poly_stride, uint64_t n, uint64_t batch, int da, int bit_reverse, g1j *d_out);   // capi_fk20.hip

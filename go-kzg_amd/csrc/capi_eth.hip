@@ -65,6 +65,7 @@ void kzg_hip_eth_settings_free(kzg_hip_eth *eth) {
     if (!eth) return;
     hipSetDevice(eth->fs->device);
     hipDeviceSynchronize();
+    eth_g2_release_passed(eth, true);
     eth->co_blob.reset(); eth->co_proof.reset();
     kzg_hip_kzg_settings_free(eth->ks);   // drains the device first
     hipFree(eth->d_domain);

@@ -139,6 +139,44 @@ int kzg_checks(hipStream_t s, const g2_prepared *gen, const g2_prepared *q1, con
 
 }  // namespace
 
+int eth_g2_lines(kzg_hip_eth *eth, std::shared_ptr<g2_state> &hold, const g2_prepared **gen, const g2_prepared **s1) {
+    hold = g2_of(eth->g2_mu, eth->g2);
+    if (!hold) return KZG_HIP_ERR_BAD_ARG;
+    *gen = hold->d_gen; *s1 = hold->d_s;
+    return KZG_HIP_OK;
+}
+void eth_g2_release_passed(kzg_hip_eth *eth, bool all) {
+    std::vector<std::shared_ptr<g2_state>> passed;   // let go after the lock, on this thread
+    {
+        std::lock_guard<std::mutex> lk(eth->g2_mu);
+        auto &q = eth->g2_queued;
+        size_t keep = 0;
+        for (auto &e : q) {
+            if (all || hipEventQuery(e.first) == hipSuccess) { (void)hipEventDestroy(e.first); passed.push_back(std::move(e.second)); }
+            else { if (&q[keep] != &e) q[keep] = std::move(e); keep++; }
+        }
+        q.resize(keep);
+        (void)hipGetLastError();                     // (hipErrorNotReady of a query)
+    }
+}
+int eth_g2_hold_on_stream(kzg_hip_eth *eth, hipStream_t s, const std::shared_ptr<g2_state> &hold) {
+    eth_g2_release_passed(eth);
+    std::lock_guard<std::mutex> lk(eth->g2_mu);
+    auto &q = eth->g2_queued;
+    hipError_t e;
+    if (!q.empty() && q.back().second == hold) {
+        e = hipEventRecord(q.back().first, s);       // the same state again: its event moves behind the new kernels (one stream, in order)
+        if (e != hipSuccess) { (void)hipStreamSynchronize(s); HIPCHK(e); }   // (the entry stays: its event is at an earlier point or this one)
+        return KZG_HIP_OK;
+    }
+    hipEvent_t ev = nullptr;
+    e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess && (e = hipEventRecord(ev, s)) != hipSuccess) (void)hipEventDestroy(ev);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); HIPCHK(e); }
+    q.emplace_back(ev, hold);
+    return KZG_HIP_OK;
+}
+
 extern "C" {
 
 int kzg_hip_g2_from_compressed(kzg_hip_fft *fs, const void *in96, uint64_t n, void *out_g2) {
@@ -282,7 +320,10 @@ int kzg_hip_check_proof_multi_batch(kzg_hip_kzg *ks, const void *commitments_g1,
 
 int kzg_hip_eth_set_setup_g2(kzg_hip_eth *eth, const void *setup_g2, uint64_t n) {
     if (!eth) return KZG_HIP_ERR_BAD_ARG;
-    return g2_state_set(eth->fs, eth->g2_mu, eth->g2, setup_g2, n);
+    int st = g2_state_set(eth->fs, eth->g2_mu, eth->g2, setup_g2, n);
+    hipSetDevice(eth->fs->device);
+    eth_g2_release_passed(eth);   // (earlier states that queued _dev calls have finished with)
+    return st;
 }
 
 int kzg_hip_eth_verify_kzg_proof_batch(kzg_hip_eth *eth, const void *commitments48, const void *zs_le32, const void *ys_le32, const void *proofs48, uint64_t count,

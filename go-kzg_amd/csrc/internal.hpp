@@ -208,6 +208,17 @@ void launch_eth_agg_finish(hipStream_t s, const uint32_t *z_in_domain, const uin
 void launch_test_sha256_lanes(hipStream_t s, const uint8_t *data, const uint64_t *offsets, const uint64_t *lens, uint64_t rows, uint32_t *out);
 void launch_test_hash_to_bls_field_lanes(hipStream_t s, const uint8_t *digests, uint64_t rows, fr *out);
 
+// ---------------- k_eth_exec.hip ----------------
+// the execution-layer side of eth/eth.go in batches (lane bodies: eth_exec.hpp)
+void launch_eth_versioned_hashes(hipStream_t s, const uint8_t *c48, uint64_t n, uint8_t *out32);   // out32[t] = KZGToVersionedHash(c48[t]); out32 4-byte aligned
+// PointEvaluationPrecompile's 192-byte rows: status 0 valid, 4 versioned hash mismatch, 2 z or y >= r, 3 undecodable commitment / proof
+void launch_eth_precompile_inputs(hipStream_t s, const uint8_t *in192, uint64_t n, g1j *p0, g1j *p1, uint8_t *status);
+void launch_eth_merge_status(hipStream_t s, const uint8_t *status, const uint8_t *ok, uint64_t n, uint8_t *result);   // result[t] = status[t] ? status[t] : ok[t]
+// VerifyKZGCommitmentsAgainstTransactions' comparison: match[t] = (KZGToVersionedHash(c48[t]) == want32[t]) over `total` commitments, then
+// result[j] = 1 when every flag of off[j] .. off[j + 1] (blocks + 1 entries) is set, else 4
+void launch_eth_tx_hashes_check(hipStream_t s, const uint8_t *c48, const uint8_t *want32, const uint64_t *off, uint64_t total, uint64_t blocks, uint8_t *match,
+                                uint8_t *result);
+
 // profiling hook (HIP events around the dominant kernel), see capi.hip
 void prof_begin(hipStream_t s, const char *name);
 void prof_end(hipStream_t s, const char *name);

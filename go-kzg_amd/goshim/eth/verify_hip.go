@@ -2,8 +2,9 @@
 // +build kzg_hip,!bignum_pure,!bignum_hol256,!bignum_hbls
 
 // eth.VerifyKZGProofBatch: eth.VerifyKZGProof (eth/eth.go:114-135) over many proofs in one device call, and VerifyAggregateKZGProofBatch /
-// ValidateBlobsSidecarBatch: the block-level verifier (eth/eth.go:155-208) over many sidecars in one device call.  A lone VerifyKZGProof (and
-// through it PointEvaluationPrecompile) and the pairing of a lone VerifyAggregateKZGProof / ValidateBlobsSidecar stay on Kilic (INTEGRATION.md).
+// ValidateBlobsSidecarBatch: the block-level verifier (eth/eth.go:155-208) over many sidecars in one device call.  A lone VerifyKZGProof, a lone
+// PointEvaluationPrecompile and the pairing of a lone VerifyAggregateKZGProof / ValidateBlobsSidecar stay on Kilic (INTEGRATION.md); batches of
+// precompile inputs are served by PointEvaluationPrecompileBatch (exec_hip.go).
 package eth
 
 /*
@@ -21,7 +22,9 @@ import (
 	"github.com/protolambda/go-kzg/bls"
 )
 
-// the eth handle that has received kzgSetupG2 (kzg_hip_eth_set_setup_g2); CloseHip (eth_hip.go) clears it with the handle
+// the eth handle that has received kzgSetupG2 (kzg_hip_eth_set_setup_g2); CloseHip (eth_hip.go) clears it with the handle.
+// hipEnsureSetupG2 (exec_hip.go) is the lock / set / mark step as a function; the two copies of it below predate it and do the same:
+// a change to that step belongs in all three places (or replaces the two copies by calls of the helper).
 var (
 	hipSetupG2Mu  sync.Mutex
 	hipSetupG2For *C.kzg_hip_eth

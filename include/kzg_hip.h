@@ -312,6 +312,51 @@ int kzg_hip_eth_compute_aggregate_kzg_proof_batch(kzg_hip_eth *eth, const void *
  * synchronisation (but for the first call's table build), transcripts always on the device.  blob_counts stays a HOST array: it sizes the launches. */
 int kzg_hip_eth_compute_aggregate_kzg_proof_batch_dev(kzg_hip_eth *eth, const void *d_blobs_le32, const uint64_t *blob_counts, uint64_t sidecars,
                                                       void *d_out_proofs48, void *d_out_commitments48, uint8_t *d_status);
+/* ---- the execution-layer side of eth/eth.go in batches: PointEvaluationPrecompile (eth/eth.go:76-110), KZGToVersionedHash (:137-141),
+ * VerifyKZGCommitmentsAgainstTransactions with TxPeekBlobVersionedHashes (:234-282) ----
+ * One result byte per input row or per block.  0 .. 3 are kzg_hip_eth_verify_kzg_proof_batch's values; the reference's checks run in the order
+ * its control flow gives, so a row or block that is wrong in several ways gets the code of the first check it fails. */
+typedef enum kzg_hip_eth_code {
+    KZG_HIP_ETH_INVALID_PROOF = 0,      /* the pairing check failed: "invalid kzg proof" */
+    KZG_HIP_ETH_VALID = 1,
+    KZG_HIP_ETH_BAD_FIELD = 2,          /* z or y not below r */
+    KZG_HIP_ETH_BAD_G1 = 3,             /* commitment or proof not a valid G1 encoding */
+    KZG_HIP_ETH_HASH_MISMATCH = 4,      /* a versioned hash does not match its commitment: "mismatched versioned hash" / "invalid version hashes vs kzg" */
+    KZG_HIP_ETH_COUNT_MISMATCH = 5,     /* number of versioned hashes != number of commitments */
+    KZG_HIP_ETH_TX_TOO_SHORT = 6,       /* "blob tx invalid: too short"; also a transaction of length 0, where the reference panics on tx[0] */
+    KZG_HIP_ETH_TX_OFFSET = 7,          /* "offset to versioned hashes is out of bounds" */
+    KZG_HIP_ETH_TX_TRAILING = 8         /* "expected trailing data starting at versioned-hashes offset to be a multiple of 32 bytes" */
+} kzg_hip_eth_code;
+/* KZGToVersionedHash over `count` commitments of 48 bytes (ANY 48 bytes: the reference hashes before it decodes): out32[i] = SHA-256 of the
+ * commitment with byte 0 replaced by BlobCommitmentVersionKZG = 0x01.  One lane per commitment; needs no G2 setup.  count == 0 is KZG_HIP_OK. */
+int kzg_hip_eth_kzg_to_versioned_hash_batch(kzg_hip_eth *eth, const void *commitments48, uint64_t count, void *out32);
+/* the same on DEVICE buffers (out32 4-byte aligned), enqueued on the handle's stream without a host synchronisation */
+int kzg_hip_eth_kzg_to_versioned_hash_batch_dev(kzg_hip_eth *eth, const void *d_commitments48, uint64_t count, void *d_out32);
+/* PointEvaluationPrecompile over `count` inputs of 192 bytes (versioned hash 32 | z 32 LE | y 32 LE | commitment 48 | proof 48): result[i] is
+ * KZG_HIP_ETH_VALID (the reference returns kzg_hip_eth_precompile_return_value's bytes), KZG_HIP_ETH_INVALID_PROOF, or the first of
+ * KZG_HIP_ETH_HASH_MISMATCH, KZG_HIP_ETH_BAD_FIELD, KZG_HIP_ETH_BAD_G1 in that order (eth/eth.go:93-107).  An input of another length
+ * ("invalid input length") is the caller's to reject.  The rows are uploaded once; the hash, the parsing and the pairing check run one lane per
+ * row and the codes come back in one download.  Needs kzg_hip_eth_set_setup_g2 (else KZG_HIP_ERR_BAD_ARG); count == 0 is KZG_HIP_OK and writes
+ * nothing; device memory is linear in count (about 500 bytes per row), the call is not chunked. */
+int kzg_hip_eth_point_evaluation_precompile_batch(kzg_hip_eth *eth, const void *inputs192, uint64_t count, uint8_t *result);
+/* the same on DEVICE buffers, enqueued on the handle's stream without a host synchronisation.  The queued kernels read the G2 setup that was
+ * current when the call was made; kzg_hip_eth_set_setup_g2 may replace it meanwhile.  The handle keeps the replaced setup until an event
+ * recorded behind those kernels has completed, and lets it go on the calling thread of the next _dev call, the next kzg_hip_eth_set_setup_g2
+ * or kzg_hip_eth_settings_free (which drains the device first), never in a stream callback. */
+int kzg_hip_eth_point_evaluation_precompile_batch_dev(kzg_hip_eth *eth, const void *d_inputs192, uint64_t count, uint8_t *d_result);
+/* precompileReturnValue (eth/globals.go:70-71): FIELD_ELEMENTS_PER_BLOB (the handle's n) as 32 big-endian bytes, then r as 32 big-endian bytes */
+int kzg_hip_eth_precompile_return_value(kzg_hip_eth *eth, void *out64);
+/* VerifyKZGCommitmentsAgainstTransactions over `blocks` blocks.  txs holds the serialized transactions of all blocks back to back; transaction t
+ * is txs[tx_offsets[t] .. tx_offsets[t + 1]) (one more offset than there are transactions, non-decreasing, else KZG_HIP_ERR_BAD_ARG);
+ * tx_counts[j] transactions and commitment_counts[j] of the 48-byte commitments belong to block j, in order.  result[j]: KZG_HIP_ETH_VALID, or
+ * the code of the block's FIRST malformed blob transaction (KZG_HIP_ETH_TX_TOO_SHORT / _TX_OFFSET / _TX_TRAILING), else
+ * KZG_HIP_ETH_COUNT_MISMATCH, else KZG_HIP_ETH_HASH_MISMATCH: the reference's precedence.  A transaction whose first byte is not 5 is skipped; a
+ * block without blob transactions and without commitments is valid; a block changes nothing in its neighbours.  The transactions are peeked
+ * on the host (five bytes each are read); the hashes and commitments of the blocks that are well formed go to the device in one upload, one lane
+ * hashes and compares each commitment, and the blocks' codes come back in one download.  Needs no G2 setup.  blocks == 0 is KZG_HIP_OK;
+ * KZG_HIP_ERR_TOO_WIDE when a sum of counts or a byte offset overflows. */
+int kzg_hip_eth_verify_kzg_commitments_against_transactions_batch(kzg_hip_eth *eth, const void *txs, const uint64_t *tx_offsets, const uint64_t *tx_counts,
+                                                                  const void *commitments48, const uint64_t *commitment_counts, uint64_t blocks, uint8_t *result);
 /* ---- erasure recovery ----
  * FFTSettings.ZeroPolyViaMultiplication (zero_poly.go:116-217): vanishing polynomial of the missing indices of a size-`length`
  * domain; writes `length` evaluations and `length` coefficients (zero-padded).  No missing index -> all zeros (:117-119). */

@@ -424,6 +424,42 @@ class Settings {
         }
         return out;
     }
+    // eth.KZGToVersionedHash over a slice (eth/eth.go:137-141)
+    std::vector<std::array<uint8_t, 32>> KZGToVersionedHashBatch(const std::vector<Bytes48> &commitments) const {
+        std::vector<std::array<uint8_t, 32>> out(commitments.size());
+        detail::must(kzg_hip_eth_kzg_to_versioned_hash_batch(h_, commitments.data(), commitments.size(), out.data()));
+        return out;
+    }
+    // eth.PointEvaluationPrecompile over inputs of PrecompileInputLength = 192 bytes (eth/eth.go:76-110): one kzg_hip_eth_code per input
+    // (KZG_HIP_ETH_VALID: the reference returns PrecompileReturnValue())
+    std::vector<uint8_t> PointEvaluationPrecompileBatch(const std::vector<std::array<uint8_t, 192>> &inputs) const {
+        std::vector<uint8_t> out(inputs.size());
+        detail::must(kzg_hip_eth_point_evaluation_precompile_batch(h_, inputs.data(), inputs.size(), out.data()));
+        return out;
+    }
+    std::array<uint8_t, 64> PrecompileReturnValue() const {                                       // eth/globals.go:70-71
+        std::array<uint8_t, 64> out{};
+        detail::must(kzg_hip_eth_precompile_return_value(h_, out.data()));
+        return out;
+    }
+    // eth.VerifyKZGCommitmentsAgainstTransactions over many blocks (eth/eth.go:261-282): transactions[j] / commitments[j] belong to block j;
+    // one kzg_hip_eth_code per block (malformed transaction > count mismatch > hash mismatch)
+    std::vector<uint8_t> VerifyKZGCommitmentsAgainstTransactionsBatch(const std::vector<std::vector<std::vector<uint8_t>>> &transactions,
+                                                                      const std::vector<std::vector<Bytes48>> &commitments) const {
+        if (commitments.size() != transactions.size()) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "slice lengths");
+        std::vector<uint8_t> out(transactions.size()), txs;
+        std::vector<uint64_t> offsets(1, 0), tx_counts, comm_counts;
+        std::vector<Bytes48> comm;
+        for (size_t j = 0; j < transactions.size(); j++) {
+            tx_counts.push_back(transactions[j].size());
+            comm_counts.push_back(commitments[j].size());
+            for (const auto &tx : transactions[j]) { txs.insert(txs.end(), tx.begin(), tx.end()); offsets.push_back(txs.size()); }
+            comm.insert(comm.end(), commitments[j].begin(), commitments[j].end());
+        }
+        detail::must(kzg_hip_eth_verify_kzg_commitments_against_transactions_batch(h_, txs.data(), offsets.data(), tx_counts.data(), comm.data(), comm_counts.data(),
+                                                                                    out.size(), out.data()));
+        return out;
+    }
 
   private:
     kzg_hip_eth *h_ = nullptr; uint64_t n_;
