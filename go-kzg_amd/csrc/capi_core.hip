@@ -401,6 +401,56 @@ int kzg_hip_fft_g1_batch_dev(kzg_hip_fft *fs, const void *d_vals_g1, uint64_t n,
     HIPCHK(hipGetLastError());
     return KZG_HIP_OK;
 }
+// ---- test hooks of the G1 transform (kzg_hip_internal.h): the plan of a stage launch, one stage launch of a forced variant, the direct passes with radix and lanes forced
+static void put_stage_plan(const g1_stage_plan &p, uint32_t *out) { out[0] = (uint32_t)p.lanes; out[1] = p.wnaf ? 1u : 0u; out[2] = p.rows ? 1u : 0u; }
+static bool g1_stage_shape_ok(kzg_hip_fft *fs, uint64_t n, uint64_t batch, uint64_t m) {
+    return n >= 2 && n <= fs->W && is_pow2(n) && m >= 1 && m <= n / 2 && is_pow2(m) && batch >= 1 && batch <= (1ull << 32) / n;
+}
+int kzg_hip_test_g1_fft_plan(kzg_hip_fft *fs, uint64_t n, uint64_t batch, uint64_t m, int dif, uint32_t out[5]) {
+    if (!fs || !out || !g1_stage_shape_ok(fs, n, batch, m)) return KZG_HIP_ERR_BAD_ARG;
+    dev_select sel(fs);       // the thresholds are the handle's device's
+    put_stage_plan(g1_fft_stage_plan(n, batch, m, dif != 0), out);
+    out[3] = g1_fft_direct_logr(n, batch);
+    out[4] = (uint32_t)g1_fft_direct_lanes(n, batch);
+    return KZG_HIP_OK;
+}
+int kzg_hip_test_g1_fft_stage(kzg_hip_fft *fs, const void *pts_g1, uint64_t n, uint64_t batch, uint64_t m, int inv, int dif, int lanes, int mul, void *out_g1, uint32_t plan_out[3]) {
+    if (!fs || !pts_g1 || !out_g1 || !g1_stage_shape_ok(fs, n, batch, m)) return KZG_HIP_ERR_BAD_ARG;
+    if ((lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4) || mul < 0 || mul > 2) return KZG_HIP_ERR_BAD_ARG;
+    stream_lease lease(fs);
+    hipStream_t s = lease.s;
+    const g1_stage_plan plan = g1_fft_stage_plan(n, batch, m, dif != 0, lanes == 0 ? -1 : lanes == 1 ? 0 : lanes == 4 ? 1 : 2,
+                                                 mul == 1 ? knobs::g1_mul_mode::regular : mul == 2 ? knobs::g1_mul_mode::wnaf : knobs::g1_mul_mode::by_shape);
+    if (plan_out) put_stage_plan(plan, plan_out);
+    dtmp<g1j> d_data(s), d_out(s);
+    CHK(d_data.alloc(n * batch)); CHK(d_out.alloc(n * batch));
+    HIPCHK(hipMemcpyAsync(d_data.p, pts_g1, n * batch * sizeof(g1j), hipMemcpyHostToDevice, s));
+    launch_g1_from_kilic(s, d_data.p, n * batch);
+    launch_g1_fft_stage_planned(s, plan, dif != 0, d_data.p, n, batch, m, inv ? fs->d_glv_reversed : fs->d_glv_expanded, inv ? fs->d_wnaf_reversed : fs->d_wnaf_expanded, fs->W);
+    launch_g1_normalize(s, d_data.p, d_out.p, n * batch, true);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_g1, d_out.p, n * batch * sizeof(g1j), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return KZG_HIP_OK;
+}
+int kzg_hip_test_g1_fft_direct(kzg_hip_fft *fs, const void *pts_g1, uint64_t n, uint64_t n_valid, uint64_t batch, int inv, uint32_t max_logr, int lanes, uint64_t n_out, void *out_g1) {
+    if (!fs || !pts_g1 || !out_g1 || n < 2 || n > fs->W || !is_pow2(n) || !n_valid || n_valid > n || n_out > n || batch < 1 || batch > (1ull << 28) / n) return KZG_HIP_ERR_BAD_ARG;
+    if (max_logr < 1 || max_logr > 4 || (lanes != 1 && lanes != 2 && lanes != 4)) return KZG_HIP_ERR_BAD_ARG;
+    stream_lease lease(fs);
+    hipStream_t s = lease.s;
+    dtmp<g1j> d_in(s), d_data(s), d_tmp(s), d_out(s);
+    CHK(d_in.alloc(n_valid * batch)); CHK(d_data.alloc(n * batch)); CHK(d_tmp.alloc(n * batch)); CHK(d_out.alloc(n * batch));
+    HIPCHK(hipMemcpyAsync(d_in.p, pts_g1, n_valid * batch * sizeof(g1j), hipMemcpyHostToDevice, s));
+    launch_g1_from_kilic(s, d_in.p, n_valid * batch);
+    HIPCHK(hipMemsetAsync(d_data.p, 0, n * batch * sizeof(g1j), s));   // the outputs a pruned last pass leaves alone: Z = 0
+    launch_g1_fft_direct(s, d_in.p, n_valid, n_valid, d_data.p, d_tmp.p, n, batch, inv ? fs->d_reversed : fs->d_expanded, fs->W, inv ? fs->d_inv_pow2 + ilog2(n) : nullptr, max_logr,
+                         lanes, 0, n_out, true);
+    launch_g1_normalize(s, d_data.p, d_out.p, n * batch, true);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_g1, d_out.p, n * batch * sizeof(g1j), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return KZG_HIP_OK;
+}
 int kzg_hip_das_fft_extension_batch_dev(kzg_hip_fft *fs, void *d_vals_fr, uint64_t n, uint64_t batch, void *stream) {
     if (!fs || !d_vals_fr) return KZG_HIP_ERR_BAD_ARG;
     if (n * 2 > fs->W) return KZG_HIP_ERR_TOO_WIDE;

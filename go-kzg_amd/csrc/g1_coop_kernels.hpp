@@ -88,13 +88,10 @@ template <bool DIF, bool WNAF, int L> __global__ __launch_bounds__(G1_BLOCK, 2) 
     }
 }
 #undef QMUL
-// the irregular width-5 NAF schedule where every wavefront holds one twiddle (L lanes x (n / 2 / m) batch butterflies per twiddle), else the regular one
-static inline bool g1_quad_wnaf(uint64_t n, uint64_t batch, uint64_t m, int lanes) {
-    return knobs::g1_mul() != knobs::g1_mul_mode::regular && ((n / 2 / m) * batch * lanes) % 64 == 0;
-}
 // these launches are at most one 256-lane workgroup per CU: 96 KiB of unused dynamic LDS keeps the dispatcher from putting two on one CU (two
 // wavefronts on a SIMD take 1.76x as long as one) while another CU stays empty
-template <bool DIF> static inline void launch_stage_coop(hipStream_t s, int lanes, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W,
+// (lanes and wn -- the width-5 NAF digit rows or the regular schedule -- are the caller's plan: g1_fft_stage_plan, k_g1.hip)
+template <bool DIF> static inline void launch_stage_coop(hipStream_t s, int lanes, bool wn, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W,
                                                   uint64_t total) {
     static const bool once = [] {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_g1_fft_stage_quad<DIF, true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
@@ -106,7 +103,6 @@ template <bool DIF> static inline void launch_stage_coop(hipStream_t s, int lane
     const size_t lds = total * lanes <= device_simd_lanes() ? 96 * 1024 : 0;
     const dim3 qg((uint32_t)((lanes * total + G1_BLOCK - 1) / G1_BLOCK));
     const uint32_t logn = ilog2(n);
-    const bool wn = g1_quad_wnaf(n, batch, m, lanes);
     if (lanes == 4) {
         if (wn) hipLaunchKernelGGL((k_g1_fft_stage_quad<DIF, true, 4>), qg, dim3(G1_BLOCK), lds, s, data, logn, m, roots, wnaf, W, total, batch);
         else hipLaunchKernelGGL((k_g1_fft_stage_quad<DIF, false, 4>), qg, dim3(G1_BLOCK), lds, s, data, logn, m, roots, wnaf, W, total, batch);

@@ -87,6 +87,15 @@ void launch_g1_bitrev_copy(hipStream_t s, const g1j *in, uint64_t in_stride, uin
 // one radix-2 DIT stage on bit-reversed data (replaces the loop of _fftG1, fft_g1.go:44-55); `roots` holds the twiddles as
 // GLV pairs (k mod lambda, k div lambda) in standard form, see g1_mul_glv
 void launch_g1_fft_stage(hipStream_t s, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W);   // wnaf: the twiddles' precomputed digit strings (KZG_WNAF_ROW bytes each)
+// Which of its device variants a stage launch runs: lanes per butterfly (1, 2 or 4), the digit schedule of the twiddle multiplication (regular odd digits or
+// width-5 NAF) and, for the NAF schedule, whether the digits come from the twiddles' precomputed rows or are recoded per butterfly.  g1_fft_stage_plan is the
+// ONE place that decides it, by launch size unless forced: quad as KZG_HIP_G1_QUAD parses (-1 by size; 0 / 1 / 2: one / four / two lanes), mul as
+// KZG_HIP_G1_MUL.  The launchers ask it with the knobs' values, the test hooks (kzg_hip_internal.h) with the caller's, and both launch through
+// launch_g1_fft_stage_planned, so what a plan says and what runs cannot differ.
+struct g1_stage_plan { int lanes; bool wnaf; bool rows; };
+g1_stage_plan g1_fft_stage_plan(uint64_t n, uint64_t batch, uint64_t m, bool dif, int quad, knobs::g1_mul_mode mul);
+g1_stage_plan g1_fft_stage_plan(uint64_t n, uint64_t batch, uint64_t m, bool dif);   // as the library's own launches choose: the knobs' values
+void launch_g1_fft_stage_planned(hipStream_t s, const g1_stage_plan &plan, bool dif, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W);
 // decimation-in-frequency stage on the same pairs / twiddles: (x, y) -> (x + y, (x - y) w); and the odd-position clear between the
 // FK20 transforms (h[:n] || inf in bit-reversed order)
 void launch_g1_fft_stage_dif(hipStream_t s, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W);
@@ -97,12 +106,13 @@ bool g1_quad_enabled();   // the stage launchers put four lanes on a butterfly f
 void launch_fb_direct_pass1(hipStream_t s, const g1a *table, uint64_t table_n, uint32_t c, uint32_t nwin, const fr *scalars, const fr *roots, uint64_t W, uint64_t batch,
                             uint32_t logR, g1j *out, bool glv = false);   // FK20 Toeplitz stage + first direct pass of the inverse transform (a lone polynomial)
 // several lanes per multiplication (g1_coop_kernels.hpp; translation units of their own)
-void launch_g1_stage_coop_dif(hipStream_t s, int lanes, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W, uint64_t total);
-void launch_g1_stage_coop_dit(hipStream_t s, int lanes, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W, uint64_t total);
+void launch_g1_stage_coop_dif(hipStream_t s, int lanes, bool wnaf_rows, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W, uint64_t total);
+void launch_g1_stage_coop_dit(hipStream_t s, int lanes, bool wnaf_rows, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W, uint64_t total);
 void launch_g1_direct_coop(hipStream_t s, int lanes, uint32_t wgs, size_t pad_lds, const g1j *src, uint64_t src_stride, uint64_t src_valid, g1j *dst, uint32_t logn, uint32_t logR,
                            uint64_t Ns, const fr *roots, uint64_t W, const fr *sc, uint64_t total, uint32_t logT, uint32_t logU);
 void launch_g1_fft_direct(hipStream_t s, const g1j *in, uint64_t in_stride, uint64_t n_valid, g1j *data, g1j *tmp, uint64_t n, uint64_t batch, const fr *roots,
-                          uint64_t W, const fr *scale, uint32_t max_logr = 4, int lanes = 1, uint32_t bits_done = 0, uint64_t n_out = 0);   // n_out: only the first n_out outputs are wanted (0 = all)
+                          uint64_t W, const fr *scale, uint32_t max_logr = 4, int lanes = 1, uint32_t bits_done = 0, uint64_t n_out = 0,   // n_out: only the first n_out outputs are wanted (0 = all)
+                          bool lanes_fixed = false);   // lanes_fixed: the pruned passes keep `lanes` too (test hook)
 // to_kilic: also leave the device-internal Montgomery domain (R' = 2^390) for Kilic's (2^384): every API output path ends here
 void launch_g1_normalize(hipStream_t s, const g1j *in, g1j *out, uint64_t n, bool to_kilic = false);
 void launch_fr_inv_test(hipStream_t s, const fr *in, uint64_t n, fr *out_coop, fr *out_lane, fr *out_block);   // test hook: F_r inversion three ways (k_fr.hip)

@@ -156,19 +156,34 @@ template <int MODE, bool PRE = false> __global__ __launch_bounds__(G1_BLOCK, 2) 
 // 4 lanes per butterfly while the quadrupled launch still fits one wavefront per SIMD (65 536 lanes on 256 CUs), 2 while the doubled one does;
 // KZG_HIP_G1_QUAD = 0 / 1 / 2: never / always four / always two
 bool g1_quad_enabled() { return knobs::g1_quad() != 0; }
-// lanes per butterfly of a stage launch: 4, 2 or 1
-static int g1_stage_lanes(uint64_t butterflies) {
-    if (const int forced = knobs::g1_quad(); forced >= 0) return forced == 0 ? 1 : forced == 2 ? 2 : 4;
-    const uint64_t one_round = device_simd_lanes();
-    return butterflies * 4 <= one_round ? 4 : butterflies * 2 <= one_round ? 2 : 1;
-}
-// The twiddles' precomputed width-5 NAF digit strings (264 bytes per twiddle in HBM) replace the per-butterfly recoding only where a
-// row is shared by many lanes (>= 512: measured +2.3 % on the 512-polynomial FK20 step); with one wavefront per twiddle every row is a
-// cold read and the recoding in registers is faster (measured -4 % on 64 transforms when the rows were always used).
 #ifndef KZG_WNAF_ROWS_MIN
 #define KZG_WNAF_ROWS_MIN 512          // lanes per twiddle from which the precomputed rows are used (A/B builds: 0 = always, 1 << 60 = never)
 #endif
-static bool g1_wnaf_rows_pay(uint64_t n, uint64_t batch, uint64_t m) { return (n / 2 / m) * batch >= (uint64_t)KZG_WNAF_ROWS_MIN; }
+// The variant of a stage launch (internal.hpp).
+//  - lanes per butterfly: 4 while the quadrupled launch still fits one wavefront per SIMD, 2 while the doubled one does, else 1.
+//  - schedule.  The width-5 NAF schedule is irregular: it only pays when the lanes of a wavefront share their twiddle.  A twiddle is shared by
+//    (n / 2 / m) * batch consecutive butterflies.  One lane each: a multiple of 64 means every wave is uniform; >= 256 means at most a quarter of the
+//    waves straddle two twiddles; otherwise (late stages of small batches: a single 4096-point transform has 64 different twiddles per wave in its
+//    last stage, measured 21 ms against 2.3 ms) the regular signed-window schedule runs instead.  KZG_HIP_G1_MUL = regular / wnaf forces one of them
+//    (A/B runs).  The one-lane DIF stage has the NAF form only.  Several lanes each: NAF where every wavefront holds exactly one twiddle (these
+//    kernels read the precomputed rows, which is only right for a wave-uniform twiddle, so "wnaf" cannot force it), else regular.
+//  - digit rows.  The twiddles' precomputed width-5 NAF digit strings (264 bytes per twiddle in HBM) replace the per-butterfly recoding only where a
+//    row is shared by many lanes (>= 512: measured +2.3 % on the 512-polynomial FK20 step); with one wavefront per twiddle every row is a
+//    cold read and the recoding in registers is faster (measured -4 % on 64 transforms when the rows were always used).
+g1_stage_plan g1_fft_stage_plan(uint64_t n, uint64_t batch, uint64_t m, bool dif, int quad, knobs::g1_mul_mode mul) {
+    const uint64_t butterflies = n / 2 * batch, per_twiddle = (n / 2 / m) * batch, one_round = device_simd_lanes();
+    g1_stage_plan p;
+    p.lanes = quad >= 0 ? (quad == 0 ? 1 : quad == 2 ? 2 : 4) : butterflies * 4 <= one_round ? 4 : butterflies * 2 <= one_round ? 2 : 1;
+    if (p.lanes > 1) {
+        p.wnaf = mul != knobs::g1_mul_mode::regular && (per_twiddle * (uint64_t)p.lanes) % 64 == 0;
+        p.rows = p.wnaf;
+        return p;
+    }
+    p.wnaf = dif || (mul == knobs::g1_mul_mode::regular ? false : mul == knobs::g1_mul_mode::wnaf ? true : (per_twiddle % 64 == 0 || per_twiddle >= 256));
+    p.rows = p.wnaf && per_twiddle >= (uint64_t)KZG_WNAF_ROWS_MIN;
+    return p;
+}
+g1_stage_plan g1_fft_stage_plan(uint64_t n, uint64_t batch, uint64_t m, bool dif) { return g1_fft_stage_plan(n, batch, m, dif, knobs::g1_quad(), knobs::g1_mul()); }
 // Decimation-in-frequency form of the same stage: (x, y) -> (x + y, (x - y) w) on the SAME pairs and twiddles (half-size m runs from
 // n / 2 down to 1, natural order in, bit-reversed order out).  Used by the FK20 inverse transform whose first two stages are folded
 // into the fixed-base Toeplitz stage (k_fb_mul_vec_dif2): the remaining stages continue here and leave h in exactly the bit-reversed
@@ -211,18 +226,7 @@ template <bool PRE> __global__ __launch_bounds__(G1_BLOCK, 2) void k_g1_fft_stag
     row[i0] = s_; row[i1] = d_;
 }
 void launch_g1_fft_stage_dif(hipStream_t s, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W) {
-    uint64_t total = n / 2 * batch;
-    if (!total) return;
-    prof_begin(s, "g1_fft_stage");
-    if (const int lanes = g1_stage_lanes(total); lanes > 1) {
-        launch_g1_stage_coop_dif(s, lanes, data, n, batch, m, roots, wnaf, W, total);
-        prof_end(s, "g1_fft_stage");
-        return;
-    }
-    const dim3 grid((uint32_t)((total + G1_BLOCK - 1) / G1_BLOCK)), block(G1_BLOCK);
-    if (g1_wnaf_rows_pay(n, batch, m)) hipLaunchKernelGGL(k_g1_fft_stage_dif<true>, grid, block, 0, s, data, ilog2(n), m, roots, wnaf, W, total, batch);
-    else hipLaunchKernelGGL(k_g1_fft_stage_dif<false>, grid, block, 0, s, data, ilog2(n), m, roots, wnaf, W, total, batch);
-    prof_end(s, "g1_fft_stage");
+    launch_g1_fft_stage_planned(s, g1_fft_stage_plan(n, batch, m, true), true, data, n, batch, m, roots, wnaf, W);
 }
 // data[b][i] = inf for every odd i: in bit-reversed order these are the coefficients k >= n / 2, i.e. the "h[:n] || inf" padding of
 // fk20_single.go:163-166 between the two transforms
@@ -245,30 +249,28 @@ void launch_g1_take_even(hipStream_t s, const g1j *in, g1j *out, uint64_t total)
     hipLaunchKernelGGL(k_g1_take_even, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, in, out, total);
 }
 void launch_g1_fft_stage(hipStream_t s, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W) {
+    launch_g1_fft_stage_planned(s, g1_fft_stage_plan(n, batch, m, false), false, data, n, batch, m, roots, wnaf, W);
+}
+// one stage launch of the variant `plan` names (a plan of g1_fft_stage_plan: the one-lane DIF stage is always NAF)
+void launch_g1_fft_stage_planned(hipStream_t s, const g1_stage_plan &plan, bool dif, g1j *data, uint64_t n, uint64_t batch, uint64_t m, const fr *roots, const int8_t *wnaf, uint64_t W) {
     uint64_t total = n / 2 * batch;
     if (!total) return;
     prof_begin(s, "g1_fft_stage");
-    // The width-5 NAF schedule is irregular: it only pays when the lanes of a wavefront share their twiddle.  A twiddle is shared by
-    // (n / 2 / m) * batch consecutive lanes: a multiple of 64 means every wave is uniform; >= 256 means at most a quarter of the
-    // waves straddle two twiddles.  Otherwise (late stages of small batches: a single 4096-point transform has 64 different
-    // twiddles per wave in its last stage, measured 21 ms against 2.3 ms) the regular signed-window schedule runs instead.
-    const knobs::g1_mul_mode forced = knobs::g1_mul();
-    const uint64_t per_twiddle = (n / 2 / m) * batch;
-    const int mode = forced == knobs::g1_mul_mode::regular ? 0 : forced == knobs::g1_mul_mode::wnaf ? 4 : ((per_twiddle % 64 == 0 || per_twiddle >= 256) ? 4 : 0);
-    if (const int lanes = g1_stage_lanes(total); lanes > 1) {
-        launch_g1_stage_coop_dit(s, lanes, data, n, batch, m, roots, wnaf, W, total);
+    if (plan.lanes > 1) {
+        if (dif) launch_g1_stage_coop_dif(s, plan.lanes, plan.wnaf, data, n, batch, m, roots, wnaf, W, total);
+        else launch_g1_stage_coop_dit(s, plan.lanes, plan.wnaf, data, n, batch, m, roots, wnaf, W, total);
         prof_end(s, "g1_fft_stage");
         return;
     }
     const dim3 grid((uint32_t)((total + G1_BLOCK - 1) / G1_BLOCK)), block(G1_BLOCK);
     const uint32_t logn = ilog2(n);
-    switch (mode) {
-    case 4:
-        if (g1_wnaf_rows_pay(n, batch, m)) hipLaunchKernelGGL((k_g1_fft_stage<4, true>), grid, block, 0, s, data, logn, m, roots, wnaf, W, total, batch);
+    if (dif) {
+        if (plan.rows) hipLaunchKernelGGL(k_g1_fft_stage_dif<true>, grid, block, 0, s, data, logn, m, roots, wnaf, W, total, batch);
+        else hipLaunchKernelGGL(k_g1_fft_stage_dif<false>, grid, block, 0, s, data, logn, m, roots, wnaf, W, total, batch);
+    } else if (plan.wnaf) {
+        if (plan.rows) hipLaunchKernelGGL((k_g1_fft_stage<4, true>), grid, block, 0, s, data, logn, m, roots, wnaf, W, total, batch);
         else hipLaunchKernelGGL((k_g1_fft_stage<4, false>), grid, block, 0, s, data, logn, m, roots, wnaf, W, total, batch);
-        break;
-    default: hipLaunchKernelGGL(k_g1_fft_stage<0>, grid, block, 0, s, data, logn, m, roots, wnaf, W, total, batch); break;
-    }
+    } else hipLaunchKernelGGL(k_g1_fft_stage<0>, grid, block, 0, s, data, logn, m, roots, wnaf, W, total, batch);
     prof_end(s, "g1_fft_stage");
 }
 
@@ -337,7 +339,7 @@ __global__ __launch_bounds__(G1_DIRECT_BLOCK, 2) void k_g1_fft_direct(const g1j 
 // runs the passes; the result lands in `data` (batch x n).  tmp: batch x n scratch points.  scale: nullptr or a device Fr that
 // multiplies every output (folded into the last pass).
 void launch_g1_fft_direct(hipStream_t s, const g1j *in, uint64_t in_stride, uint64_t n_valid, g1j *data, g1j *tmp, uint64_t n, uint64_t batch, const fr *roots,
-                          uint64_t W, const fr *scale, uint32_t max_logr, int lanes, uint32_t bits_done, uint64_t n_out) {
+                          uint64_t W, const fr *scale, uint32_t max_logr, int lanes, uint32_t bits_done, uint64_t n_out, bool lanes_fixed) {
     const uint32_t logn = ilog2(n);
     if (max_logr < 1 || max_logr > 4) max_logr = 4;
     // bits_done > 0: `in` already holds the result of the passes over the first bits_done bits (launch_fb_direct_pass1); continue from there
@@ -359,7 +361,7 @@ void launch_g1_fft_direct(hipStream_t s, const g1j *in, uint64_t in_stride, uint
         const uint64_t total = (batch * cols) << (logT + logU);
         // as many lanes per term as keep the pass at one wavefront per SIMD (the caller's choice for full passes; pruned ones may take more)
         int L = lanes;
-        if (g1_quad_enabled() && knobs::g1_direct_coop() && (logT < logR || logU < logR)) L = total * 4 <= device_simd_lanes() ? 4 : total * 2 <= device_simd_lanes() ? 2 : lanes;
+        if (!lanes_fixed && g1_quad_enabled() && knobs::g1_direct_coop() && (logT < logR || logU < logR)) L = total * 4 <= device_simd_lanes() ? 4 : total * 2 <= device_simd_lanes() ? 2 : lanes;
         // 24 KiB of unused dynamic LDS on top of the 10 KiB the kernel needs: at most 4 of these one-wave workgroups fit a CU, so the
         // 1024 of a 4096-point pass land one per SIMD instead of 8 per CU on half of the chip (measured: 2.7 vs 5.4 ms per pass)
         // (only while the pass has at most one wavefront per SIMD: two transforms are 2048 workgroups and want both wave slots)

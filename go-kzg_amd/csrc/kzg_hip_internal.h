@@ -1,7 +1,7 @@
 /*
  * kzg_hip_internal.h -- instrumentation exports of libkzg_hip.so that are NOT part of the drop-in boundary (include/kzg_hip.h): the hooks
  * bench.py, tools/ and the tests use to measure and to check the library from outside.  A Go / cgo caller never needs them; they are exported
- * (default visibility) only so that ctypes can reach them.  Implemented in capi_bench.hip (and capi_eth.hip for the SHA-256 hook).
+ * (default visibility) only so that ctypes can reach them.  Implemented in capi_bench.hip (capi_eth.hip for the SHA-256 hook, capi_core.hip for the G1 transform's).
  */
 #ifndef KZG_HIP_INTERNAL_H
 #define KZG_HIP_INTERNAL_H
@@ -63,6 +63,25 @@ int kzg_hip_pairing_test(kzg_hip_fft *fs, const void *g1, const void *g2, uint64
 /* test hook of the G2 half of a setup (capi_verify.hip): how many times the handle built its fixed-base table of bls.GenG2 -- 0 before the first
  * kzg_hip_g2_mul_generator_vec / kzg_hip_generate_testing_setup_g2, 1 ever after, however many threads made the first call at once */
 int kzg_hip_test_g2_table_builds(kzg_hip_fft *fs, uint64_t *builds);
+
+/* test hooks of the G1 transform (capi_core.hip).  A stage launch of the radix-2 network runs one of 13 device variants; g1_fft_stage_plan (k_g1.hip) chooses it and
+ * these hooks report and force its choice.  A plan is three words: lanes per butterfly (1, 2, 4), schedule of the twiddle multiplication (0 regular odd digits, 1
+ * width-5 NAF), digits from the twiddles' precomputed rows (0 / 1).
+ * kzg_hip_test_g1_fft_plan: out[0..2] = the plan the library chooses, by size and by the environment's switches, for the stage of half-size m of `batch` transforms
+ * of n points (dif: the decimation-in-frequency stage); out[3] = log2 of the radix of the direct passes for (n, batch), 0 = the radix-2 network; out[4] = their lanes
+ * per (output, term). */
+int kzg_hip_test_g1_fft_plan(kzg_hip_fft *fs, uint64_t n, uint64_t batch, uint64_t m, int dif, uint32_t out[5]);
+/* runs exactly ONE stage launch on batch x n caller points (Kilic images with any Jacobian Z, host buffers), taken as the stage's input state as they are (no bit
+ * reversal): butterflies (i0, i1 = i0 + m), i0 = g 2m + j, twiddle roots[j W / (2m)] of the reversed (inv) or expanded table; DIT (x + w y, x - w y), DIF
+ * (x + y, (x - y) w).  lanes: 0 by size, 1, 2, 4; mul: 0 by shape, 1 regular, 2 wnaf -- what KZG_HIP_G1_QUAD and KZG_HIP_G1_MUL force per process, per call (with
+ * several lanes the NAF schedule runs only where every wavefront holds one twiddle, forced or not).  out_g1: normalised Kilic images; plan_out (nullable): the plan that ran */
+int kzg_hip_test_g1_fft_stage(kzg_hip_fft *fs, const void *pts_g1, uint64_t n, uint64_t batch, uint64_t m, int inv, int dif, int lanes, int mul, void *out_g1,
+                              uint32_t plan_out[3]);
+/* a whole transform on the direct passes (launch_g1_fft_direct) with the radix 2^max_logr (1 .. 4) and the lanes per (output, term) (1, 2, 4) of EVERY pass forced.
+ * pts_g1: batch rows of n_valid points, zero-padded to n on the device; inv folds 1 / n into the last pass; n_out: 0, or only the first n_out outputs of each row
+ * are computed (the rest of out_g1, batch x n normalised Kilic images, is unspecified) */
+int kzg_hip_test_g1_fft_direct(kzg_hip_fft *fs, const void *pts_g1, uint64_t n, uint64_t n_valid, uint64_t batch, int inv, uint32_t max_logr, int lanes, uint64_t n_out,
+                               void *out_g1);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
