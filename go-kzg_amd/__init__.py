@@ -109,6 +109,8 @@ def lib():
         "kzg_hip_eth_verify_kzg_commitments_against_transactions_batch": (i32, [vp, vp, vp, vp, vp, vp, u64, vp]),
         "kzg_hip_test_sha256_lanes": (i32, [vp, vp, vp, vp, u64, vp]), "kzg_hip_test_hash_to_bls_field_lanes": (i32, [vp, vp, u64, vp]),
         "kzg_hip_pairing_test": (i32, [vp, vp, vp, u64, vp]),
+        "kzg_hip_pairing_test_wave": (i32, [vp, vp, vp, u64, vp]), "kzg_hip_test_wave_fp12_op": (i32, [vp, i32, vp, vp, u64, vp]),
+        "kzg_hip_test_pairing_route": (i32, [u64, C.POINTER(u64)]),
         "kzg_hip_toeplitz_part2": (i32, [vp, vp, vp, u64, vp]), "kzg_hip_toeplitz_part3": (i32, [vp, vp, u64, vp]),
         "kzg_hip_fk20_single_settings_new": (i32, [vp, u64, pp]), "kzg_hip_fk20_single_settings_free": (None, [vp]),
         "kzg_hip_fk20_single_x_ext_fft": (i32, [vp, vp]), "kzg_hip_fk20_single": (i32, [vp, vp, u64, vp]),
@@ -234,6 +236,13 @@ def _g1(a):
 def _g2(a):
     a = np.ascontiguousarray(a, dtype=np.uint64)
     return a.reshape(-1, 3, 2, 6)
+
+
+def pairing_route(n):
+    """test hook: ("wave" | "lane", PAIRING_WAVE_BELOW): the kernel a batch of n pairing checks runs under the current environment"""
+    out = (C.c_uint64 * 2)()
+    _chk(lib().kzg_hip_test_pairing_route(n, out))
+    return ("wave" if out[0] else "lane"), int(out[1])
 
 
 def g2_empty(n):
@@ -446,6 +455,22 @@ class FFTSettings:
         out = np.zeros((n, 12, 6), dtype=np.uint64)
         _chk(lib().kzg_hip_pairing_test(self.h, _p(g1), _p(g2), n, _p(out)))
         return [[sum(int(v[k][i]) << (64 * i) for i in range(6)) for k in range(12)] for v in out]
+
+    def pairing_test_wave(self, g1, g2):
+        """test hook: pairing_test on the kernel with one wavefront per pair"""
+        g1, g2 = _g1(g1), _g2(g2)
+        n = g1.shape[0]
+        out = np.zeros((n, 12, 6), dtype=np.uint64)
+        _chk(lib().kzg_hip_pairing_test_wave(self.h, _p(g1), _p(g2), n, _p(out)))
+        return [[sum(int(v[k][i]) << (64 * i) for i in range(6)) for k in range(12)] for v in out]
+
+    def wave_fp12_op(self, op, a, b):
+        """test hook: one tower operation per row on the wavefront tower; a, b: (n, 144) uint32 rows of 12 standard-form F_p elements"""
+        a, b = np.ascontiguousarray(a, dtype=np.uint32), np.ascontiguousarray(b, dtype=np.uint32)
+        assert a.shape == b.shape and a.ndim == 2 and a.shape[1] == 144
+        out = np.zeros_like(a)
+        _chk(lib().kzg_hip_test_wave_fp12_op(self.h, op, _p(a), _p(b), a.shape[0], _p(out)))
+        return out
 
     def g1_marshal_text(self, points):
         """bls.G1Point.MarshalText over a slice (bls/bls_all.go:20-22): lower-case hex of the 48-byte compressed form"""

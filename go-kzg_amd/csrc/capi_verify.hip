@@ -513,8 +513,8 @@ int kzg_hip_test_hash_to_bls_field_lanes(kzg_hip_fft *fs, const void *digests32,
     KZG_CATCH
 }
 
-// test hook (kzg_hip_internal.h): out[i] = reduced e(g1[i], g2[i]) as 12 standard-form F_p elements
-int kzg_hip_pairing_test(kzg_hip_fft *fs, const void *g1, const void *g2, uint64_t n, void *out_fp12) {
+// test hooks (kzg_hip_internal.h): out[i] = reduced e(g1[i], g2[i]) as 12 standard-form F_p elements, by the one-lane or the wavefront kernel
+static int pairing_test(kzg_hip_fft *fs, const void *g1, const void *g2, uint64_t n, void *out_fp12, bool wave) {
     if (!fs || (n && (!g1 || !g2 || !out_fp12))) return KZG_HIP_ERR_BAD_ARG;
     if (!n) return KZG_HIP_OK;
     KZG_TRY
@@ -528,12 +528,41 @@ int kzg_hip_pairing_test(kzg_hip_fft *fs, const void *g1, const void *g2, uint64
     HIPCHK(hipMemcpyAsync(d_p.p, g1, n * sizeof(g1j), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_q.p, g2, n * sizeof(g2j), hipMemcpyHostToDevice, s));
     launch_g2_prepare(s, d_q.p, n, d_lines);
-    launch_pairing_value(s, d_p.p, d_lines, n, d_out.p);
+    if (wave) launch_pairing_value_wave(s, d_p.p, d_lines, n, d_out.p);
+    else launch_pairing_value(s, d_p.p, d_lines, n, d_out.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_fp12, d_out.p, 12 * n * sizeof(fp), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return KZG_HIP_OK;
     KZG_CATCH
+}
+int kzg_hip_pairing_test(kzg_hip_fft *fs, const void *g1, const void *g2, uint64_t n, void *out_fp12) { return pairing_test(fs, g1, g2, n, out_fp12, false); }
+int kzg_hip_pairing_test_wave(kzg_hip_fft *fs, const void *g1, const void *g2, uint64_t n, void *out_fp12) { return pairing_test(fs, g1, g2, n, out_fp12, true); }
+
+// test hook: out[i] = op(a[i], b[i]) on the wavefront tower (k_wave_fp12_op), rows of 12 standard-form F_p elements
+int kzg_hip_test_wave_fp12_op(kzg_hip_fft *fs, int op, const void *a, const void *b, uint64_t n, void *out) {
+    if (!fs || op < 0 || op > 8 || (n && (!a || !b || !out))) return KZG_HIP_ERR_BAD_ARG;
+    if (!n) return KZG_HIP_OK;
+    KZG_TRY
+    stream_lease lease(fs);
+    hipStream_t s = lease.s;
+    dtmp<fp> d_a(s), d_b(s), d_out(s);
+    CHK(d_a.alloc(12 * n)); CHK(d_b.alloc(12 * n)); CHK(d_out.alloc(12 * n));
+    HIPCHK(hipMemcpyAsync(d_a.p, a, 12 * n * sizeof(fp), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_b.p, b, 12 * n * sizeof(fp), hipMemcpyHostToDevice, s));
+    launch_wave_fp12_op(s, op, d_a.p, d_b.p, n, d_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out.p, 12 * n * sizeof(fp), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return KZG_HIP_OK;
+    KZG_CATCH
+}
+// test hook: out[0] = 1 when launch_pairing_check would run the wavefront kernel for n checks now, 0 for the one-lane kernel; out[1] = PAIRING_WAVE_BELOW
+int kzg_hip_test_pairing_route(uint64_t n, uint64_t *out) {
+    if (!out) return KZG_HIP_ERR_BAD_ARG;
+    out[0] = pairing_route_is_wave(n) ? 1 : 0;
+    out[1] = PAIRING_WAVE_BELOW;
+    return KZG_HIP_OK;
 }
 
 }  // extern "C"

@@ -182,6 +182,16 @@ void launch_eth_check_inputs(hipStream_t s, const uint8_t *c48, const uint8_t *z
 // ok[i] = e(p0[i], Q0) e(p1[i], Q1) == 1; shared_lines: Q0 = q0[0], Q1 = q1[0] for every check, else q0[i], q1[i]
 void launch_pairing_check(hipStream_t s, bool shared_lines, const g2_prepared *q0, const g2_prepared *q1, const g1j *p0, const g1j *p1, uint64_t n, uint8_t *ok);
 void launch_pairing_value(hipStream_t s, const g1j *g1_kilic, const g2_prepared *q, uint64_t n, fp *out);   // test hook: reduced e(g1[i], Q_i), standard form
+bool pairing_route_is_wave(uint64_t n);   // which kernel launch_pairing_check runs for n checks under the current environment (KZG_HIP_PAIRING)
+
+// ---------------- k_pairing_wave.hip ----------------
+// the same check with one wavefront (one workgroup) per check (wave_pairing.hpp): the route of launch_pairing_check below PAIRING_WAVE_BELOW checks
+// Measured (profiles/verify.md, both routes in one run on one MI355X, best of three): the wavefront kernel is faster at every count up to 16 384
+// (1: 7.9 against 39.1 ms, 8192: 22.0 against 44.7, 16 384: 39.2 against 47.6; spreads below 0.2 ms); 65 536 was measured on the lane route only
+constexpr uint64_t PAIRING_WAVE_BELOW = 16385;
+void launch_pairing_check_wave(hipStream_t s, bool shared_lines, const g2_prepared *q0, const g2_prepared *q1, const g1j *p0, const g1j *p1, uint64_t n, uint8_t *ok);
+void launch_pairing_value_wave(hipStream_t s, const g1j *g1_kilic, const g2_prepared *q, uint64_t n, fp *out);   // test hook: launch_pairing_value's twin
+void launch_wave_fp12_op(hipStream_t s, int op, const fp *a, const fp *b, uint64_t n, fp *out);                  // test hook: one tower operation per workgroup, standard form
 
 // ---------------- k_g2.hip ----------------
 // the G2 half of a setup (g2.hpp): the fixed-base table of bls.GenG2 (G2_FB_ENTRIES affine entries, device-internal domain), the walk over it

@@ -102,8 +102,19 @@ __global__ __launch_bounds__(PAIRING_BLOCK) void k_pairing_check(const g2_prepar
     g1j p[2] = {p0[t], p1[t]};
     ok[t] = pairing_product_is_one<2>(q, p) ? 1 : 0;
 }
+// one wavefront per check (k_pairing_wave.hip) below PAIRING_WAVE_BELOW checks, one lane per check from there on; KZG_HIP_PAIRING forces either
+bool pairing_route_is_wave(uint64_t n) {
+    const knobs::pairing_mode forced = knobs::pairing();
+    return forced == knobs::pairing_mode::by_count ? n < PAIRING_WAVE_BELOW : forced == knobs::pairing_mode::wave;
+}
 void launch_pairing_check(hipStream_t s, bool shared_lines, const g2_prepared *q0, const g2_prepared *q1, const g1j *p0, const g1j *p1, uint64_t n, uint8_t *ok) {
     if (!n) return;
+    if (pairing_route_is_wave(n)) {
+        prof_begin(s, "pairing_check_wave");
+        launch_pairing_check_wave(s, shared_lines, q0, q1, p0, p1, n, ok);
+        prof_end(s, "pairing_check_wave");
+        return;
+    }
     prof_begin(s, "pairing_check");
     if (shared_lines) hipLaunchKernelGGL(k_pairing_check<true>, pairing_grid(n), dim3(PAIRING_BLOCK), 0, s, q0, q1, p0, p1, n, ok);
     else hipLaunchKernelGGL(k_pairing_check<false>, pairing_grid(n), dim3(PAIRING_BLOCK), 0, s, q0, q1, p0, p1, n, ok);

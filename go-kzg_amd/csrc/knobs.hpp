@@ -30,6 +30,7 @@ enum class fr_fft_mode { by_size, radix2, shared };
 enum class zero_poly_mode { by_size, direct, tree };
 enum class msm_reduce_mode { by_batch, scan, chunks };
 enum class transcript_mode { by_count, host, device };
+enum class pairing_mode { by_count, lane, wave };
 enum class transport_mode { by_devices, rccl, host, peer };
 struct opt_gb { bool set; double gb; };   // a table budget: unset leaves the size to the caller's policy
 
@@ -90,6 +91,7 @@ KZG_KNOB_PER_CALL(zero_poly_mode, zero_poly_per_call, "KZG_HIP_ZERO_POLY", zero_
 KZG_KNOB_ONCE(msm_reduce_mode, msm_reduce, "KZG_HIP_MSM_REDUCE", is(e, "chunks") ? msm_reduce_mode::chunks : is(e, "scan") ? msm_reduce_mode::scan : msm_reduce_mode::by_batch)   // bucket MSM: force a reduce form (A/B runs, tests)
 KZG_KNOB_ONCE(int, msm_seg, "KZG_HIP_MSM_SEG", e ? atoi(e) : -1)                                                                            // bucket MSM: 0 / 1 never / always the balanced accumulate; any other number: by batch
 KZG_KNOB_PER_CALL(transcript_mode, eth_transcript, "KZG_HIP_ETH_TRANSCRIPT", is(e, "host") ? transcript_mode::host : is(e, "device") ? transcript_mode::device : transcript_mode::by_count)   // where the aggregate verifier and the batched aggregate prover hash
+KZG_KNOB_PER_CALL(pairing_mode, pairing, "KZG_HIP_PAIRING", is(e, "lane") ? pairing_mode::lane : is(e, "wave") ? pairing_mode::wave : pairing_mode::by_count)   // the kernel of every pairing check: one lane or one wavefront per check (launch_pairing_check; tests, A/B runs)
 KZG_KNOB_PER_CALL(int, multi_fft, "KZG_HIP_MULTI_FFT", !e ? -1 : is(e, "sharded") ? 1 : 0)                                                   // -1 the handle's policy; "sharded" 1; ANY other value gathers (0)
 KZG_KNOB_PER_HANDLE(transport_mode, multi_transport, "KZG_HIP_MULTI_TRANSPORT", !e ? transport_mode::by_devices : is(e, "rccl") ? transport_mode::rccl : is(e, "host") ? transport_mode::host : transport_mode::peer)   // any other value: peer copies, RCCL is not bound
 KZG_KNOB_PER_HANDLE(unsigned, multi_fault, "KZG_HIP_MULTI_FAULT", multi_fault_of(e))                                                        // tests: a comma-separated list of legs of the exchange that fail, FAULT_* above

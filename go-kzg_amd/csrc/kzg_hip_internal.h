@@ -59,6 +59,14 @@ uint64_t kzg_hip_test_eth_prove_chunks(void);
 /* test hook of the pairing (k_pairing.hip): out_fp12[i] = e(g1[i], g2[i]) raised to 3 (p^12 - 1) / r (the exponent of pairing.hpp's final
  * exponentiation), 12 F_p elements of 48 bytes each in STANDARD form, order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1; G1 / G2 Kilic images in */
 int kzg_hip_pairing_test(kzg_hip_fft *fs, const void *g1, const void *g2, uint64_t n, void *out_fp12);
+/* its twin on the kernel with one wavefront per check (k_pairing_wave.hip): the same bytes */
+int kzg_hip_pairing_test_wave(kzg_hip_fft *fs, const void *g1, const void *g2, uint64_t n, void *out_fp12);
+/* test hook of the tower on a wavefront (wave_tower.hpp): out[i] = op(a[i], b[i]), one workgroup per row, rows of 12 F_p elements in STANDARD form.
+ * op: 0 mul, 1 sqr, 2 inv, 3 frob, 4 frob2, 5 frob3, 6 cyclotomic sqr, 7 conj, 8 mul_014 (b holds c0, c1, c4 as its first three F_p2) */
+int kzg_hip_test_wave_fp12_op(kzg_hip_fft *fs, int op, const void *a, const void *b, uint64_t n, void *out);
+/* which kernel launch_pairing_check would run for n checks under the current environment (KZG_HIP_PAIRING = lane / wave, read per call):
+ * out[0] = 1 one wavefront per check, 0 one lane per check; out[1] = the count below which the wavefront kernel is the default */
+int kzg_hip_test_pairing_route(uint64_t n, uint64_t out[2]);
 
 /* test hook of the G2 half of a setup (capi_verify.hip): how many times the handle built its fixed-base table of bls.GenG2 -- 0 before the first
  * kzg_hip_g2_mul_generator_vec / kzg_hip_generate_testing_setup_g2, 1 ever after, however many threads made the first call at once */

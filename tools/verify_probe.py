@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Wall time of the batched verifiers (capi_verify.hip) at count 1, 64, 4096 and 65 536: KZGSettings.check_proof_single_batch on the
-reference's 16-coefficient setup and EthSettings.verify_kzg_proof_batch on the trusted setup.  Prints one JSON line; profiles/verify.md
-records a run.  The only check: a 4096-check batch takes less than 40 times a single check (the lanes run in parallel)."""
+"""Wall time of the batched verifiers (capi_verify.hip) on BOTH routes of the pairing check (KZG_HIP_PAIRING=lane: one lane per check,
+=wave: one wavefront per check) at count 1, 64, 1024, 4096, 8192 and 16 384, the lane route also at 65 536: KZGSettings.check_proof_single_batch
+on the reference's 16-coefficient setup and EthSettings.verify_kzg_proof_batch on the trusted setup, host buffers, best and worst of three
+repeats ([best, worst] ms).  A library without the switch (an older build through KZG_HIP_LIB) runs its one route under "lane".  Prints one JSON
+line; profiles/verify.md records a run.  The only check: on the lane route a 4096-check batch takes less than 40 times a single check."""
 import json
 import os
 import sys
@@ -16,7 +18,8 @@ import gokzg_amd as kz  # noqa: E402
 import pairing_ref as pr  # noqa: E402
 from oracle import koracle as ko  # noqa: E402
 
-COUNTS = [1, 64, 4096, 65536]
+COUNTS = [1, 64, 1024, 4096, 8192, 16384, 65536]
+WAVE_MAX = 16384
 R384 = pow(2, 384, pr.P)
 
 
@@ -33,6 +36,30 @@ def timed(f, reps=3):
     return best * 1e3
 
 
+def routes():
+    try:
+        kz.pairing_route(1)
+    except AttributeError:          # a library from before the switch
+        return ["lane"]
+    return ["lane", "wave"]
+
+
+def both(f, n):
+    """{route: [best, worst] ms of three calls after a warm-up}; the routes alternate per count"""
+    out = {}
+    for route in routes():
+        if route == "wave" and n > WAVE_MAX:
+            continue
+        os.environ["KZG_HIP_PAIRING"] = route
+        f()
+        ts = []
+        for _ in range(3):
+            t = time.perf_counter(); f(); ts.append((time.perf_counter() - t) * 1e3)
+        out[route] = [round(min(ts), 3), round(max(ts), 3)]
+    os.environ.pop("KZG_HIP_PAIRING", None)
+    return out
+
+
 def main():
     s = 1927409816240961209460912649124
     fs = kz.FFTSettings(4)
@@ -47,7 +74,7 @@ def main():
     for n in COUNTS:
         cs, ps, xs, ys = np.stack([c] * n), np.stack([pi] * n), ko.fr_from_ints([17] * n), ko.fr_from_ints([y] * n)
         assert ks.check_proof_single_batch(cs, ps, xs, ys).all()
-        res["check_proof_single_batch_ms"][n] = round(timed(lambda: ks.check_proof_single_batch(cs, ps, xs, ys), 1 if n > 4096 else 3), 3)
+        res["check_proof_single_batch_ms"][n] = both(lambda: ks.check_proof_single_batch(cs, ps, xs, ys), n)
     # CheckProofMulti over rows (coset of 8 at x = 5431, the reference's kzg_multi_proofs_test.go): interpolation commitments batched too
     fs8 = kz.FFTSettings(3)
     ks8 = kz.KZGSettings(fs8, ko.generate_testing_setup_g1(s, 9))
@@ -60,7 +87,7 @@ def main():
     ysm = ko.fr_from_ints([sum(v * pow(x * w, i, ko.R_MOD) for i, v in enumerate(poly_i)) % ko.R_MOD for w in roots])
     pim = ks8.compute_proof_multi(poly, x, 8)
     res["check_proof_multi_batch_ms"] = {}
-    for n in COUNTS[:3]:
+    for n in (1, 64, 4096):
         cs, ps, xs, ys = np.stack([c] * n), np.stack([pim] * n), ko.fr_from_ints([x] * n), np.stack([ysm] * n)
         assert ks8.check_proof_multi_batch(cs, ps, xs, ys).all()
         res["check_proof_multi_batch_ms"][n] = round(timed(lambda: ks8.check_proof_multi_batch(cs, ps, xs, ys)), 3)
@@ -79,9 +106,10 @@ def main():
     for n in COUNTS:
         C_, Z, Y, P_ = np.stack([cb] * n), np.stack([zb] * n), np.stack([yb] * n), np.stack([proof] * n)
         assert (eth.verify_kzg_proof_batch(C_, Z, Y, P_) == 1).all()
-        res["eth_verify_kzg_proof_batch_ms"][n] = round(timed(lambda: eth.verify_kzg_proof_batch(C_, Z, Y, P_), 1 if n > 4096 else 3), 3)
+        res["eth_verify_kzg_proof_batch_ms"][n] = both(lambda: eth.verify_kzg_proof_batch(C_, Z, Y, P_), n)
     t = res["check_proof_single_batch_ms"]
-    res["parallel_sanity_4096_lt_40x_single"] = t[4096] < 40 * t[1]
+    res["parallel_sanity_4096_lt_40x_single"] = t[4096]["lane"][0] < 40 * t[1]["lane"][0]
+    res["pairing_wave_below"] = kz.pairing_route(1)[1] if len(routes()) == 2 else None
     print(json.dumps(res))
     return 0 if res["parallel_sanity_4096_lt_40x_single"] else 1
 
