@@ -100,6 +100,9 @@ def lib():
         "kzg_hip_test_g2_table_builds": (i32, [vp, C.POINTER(u64)]),
         "kzg_hip_kzg_set_secret_g2": (i32, [vp, vp, u64]), "kzg_hip_check_proof_single_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "kzg_hip_check_proof_multi_batch": (i32, [vp, vp, vp, vp, vp, u64, u64, vp]),
+        "kzg_hip_check_proof_single_batch_combined": (i32, [vp, vp, vp, vp, vp, u64, vp, vp]),
+        "kzg_hip_eth_verify_kzg_proof_batch_combined": (i32, [vp, vp, vp, vp, vp, u64, vp, vp]),
+        "kzg_hip_test_combine_points": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, vp]), "kzg_hip_test_combine_stats": (i32, [C.POINTER(u64)]),
         "kzg_hip_eth_set_setup_g2": (i32, [vp, vp, u64]), "kzg_hip_eth_verify_kzg_proof_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "kzg_hip_eth_verify_aggregate_kzg_proof_batch": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]),
         "kzg_hip_eth_kzg_to_versioned_hash_batch": (i32, [vp, vp, u64, vp]), "kzg_hip_eth_kzg_to_versioned_hash_batch_dev": (i32, [vp, vp, u64, vp]),
@@ -236,6 +239,25 @@ def _g1(a):
 def _g2(a):
     a = np.ascontiguousarray(a, dtype=np.uint64)
     return a.reshape(-1, 3, 2, 6)
+
+
+def _seed32(seed):
+    """None, or the 32 bytes of a combination seed as a ctypes buffer"""
+    if seed is None:
+        return None
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise KzgError(ERR_LEN_MISMATCH, "a seed is 32 bytes")
+    return C.c_char_p(seed)
+
+
+def combine_stats():
+    """test hook: what the calling thread's last _combined proof check did, and the routing now: dict(route = "combined" | "per_row", groups,
+    failed, rechecked, combine_from, rows)"""
+    out = (C.c_uint64 * 6)()
+    _chk(lib().kzg_hip_test_combine_stats(out))
+    return {"route": "combined" if out[0] else "per_row", "groups": int(out[1]), "failed": int(out[2]), "rechecked": int(out[3]),
+            "combine_from": int(out[4]), "rows": int(out[5])}
 
 
 def pairing_route(n):
@@ -730,6 +752,27 @@ class KZGSettings:
         _chk(lib().kzg_hip_check_proof_single_batch(self.h, _p(c), _p(pi), _p(xs), _p(ys), n, _p(ok)))
         return ok.astype(bool)
 
+    def check_proof_single_batch_combined(self, commitments, proofs, xs, ys, seed=None):
+        """the same mask with one pairing check per group of rows (kzg_hip_check_proof_single_batch_combined): a random linear combination per
+        group, the rows of a failing group re-checked one by one.  seed: 32 bytes for reproducible runs, None: drawn from the operating system
+        (a seed the prover can know in advance voids the 2^-128 bound).  Presupposes points of G1, as CheckProofSingle does"""
+        c, pi, xs, ys = _g1(commitments), _g1(proofs), _fr(xs), _fr(ys)
+        n = c.shape[0]
+        if not (pi.shape[0] == xs.shape[0] == ys.shape[0] == n):
+            raise KzgError(ERR_LEN_MISMATCH, "one commitment, proof, x and y per check")
+        ok = np.zeros(n, dtype=np.uint8)
+        _chk(lib().kzg_hip_check_proof_single_batch_combined(self.h, _p(c), _p(pi), _p(xs), _p(ys), n, _seed32(seed), _p(ok)))
+        return ok.astype(bool)
+
+    def test_combine_points(self, commitments, proofs, xs, ys, seed):
+        """test hook: (A_g, B_g) of every group of the combined check for these inputs and this seed, normalised images"""
+        c, pi, xs, ys = _g1(commitments), _g1(proofs), _fr(xs), _fr(ys)
+        n = c.shape[0]
+        groups = -(-n // combine_stats()["rows"])
+        a, b = g1_empty(groups), g1_empty(groups)
+        _chk(lib().kzg_hip_test_combine_points(self.h, _p(c), _p(pi), _p(xs), _p(ys), n, _seed32(seed), _p(a), _p(b)))
+        return a, b
+
     def check_proof_multi_batch(self, commitments, proofs, xs, ys):
         """KZGSettings.CheckProofMulti (kzg_multi_proofs.go:47-75) over rows; ys is (count, n, 4) -> bool mask"""
         c, pi, xs = _g1(commitments), _g1(proofs), _fr(xs)
@@ -1110,6 +1153,20 @@ class EthSettings:
             raise KzgError(ERR_LEN_MISMATCH, "one commitment, z, y and proof per check")
         out = np.zeros(n, dtype=np.uint8)
         _chk(lib().kzg_hip_eth_verify_kzg_proof_batch(self.h, _p(c), _p(zs), _p(ys), _p(pi), n, _p(out)))
+        return out
+
+    def verify_kzg_proof_batch_combined(self, commitments, zs, ys, proofs, seed=None):
+        """the same codes with one pairing check per group of rows (kzg_hip_eth_verify_kzg_proof_batch_combined): rows with code 2 or 3 drop out of
+        their group's combination, the rows of a failing group are re-checked one by one.  seed as KZGSettings.check_proof_single_batch_combined"""
+        c = np.ascontiguousarray(commitments, dtype=np.uint8).reshape(-1, 48)
+        pi = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, 48)
+        zs = np.ascontiguousarray(zs, dtype=np.uint8).reshape(-1, 32)
+        ys = np.ascontiguousarray(ys, dtype=np.uint8).reshape(-1, 32)
+        n = c.shape[0]
+        if not (pi.shape[0] == zs.shape[0] == ys.shape[0] == n):
+            raise KzgError(ERR_LEN_MISMATCH, "one commitment, z, y and proof per check")
+        out = np.zeros(n, dtype=np.uint8)
+        _chk(lib().kzg_hip_eth_verify_kzg_proof_batch_combined(self.h, _p(c), _p(zs), _p(ys), _p(pi), n, _seed32(seed), _p(out)))
         return out
 
     def kzg_to_versioned_hash_batch(self, commitments):

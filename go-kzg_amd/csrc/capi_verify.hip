@@ -4,6 +4,9 @@
 #include "capi_common.hpp"
 #include "pairing.hpp"
 #include "sha256_lane.hpp"
+#include "verify_combine.hpp"
+#include <random>
+#include <sys/random.h>
 
 // G2 points a handle verifies against: the caller's array (Kilic images) and its prepared points, [1]G2 and [s]G2 at once, [s^n]G2 on first use.
 // Thread safety: the handle's pointer to its state is read and replaced under the handle's g2_mu (g2_of / g2_state_set); every check holds its
@@ -135,6 +138,102 @@ int kzg_checks(hipStream_t s, const g2_prepared *gen, const g2_prepared *q1, con
     launch_kzg_check_inputs(s, d_c.p, d_pi.p, ys_fr ? d_y.p : nullptr, d_es, ys_fr ? d_b.p : d_bs, count, d_p0.p, d_p1.p);
     HIPCHK(hipGetLastError());
     return run_shared_check(s, gen, q1, d_p0.p, d_p1.p, count, ok);
+}
+
+// eth.VerifyKZGProof over `count` rows of bytes, one pairing check per row: result[i] = 1 / 0, or the row's status 2 / 3
+int eth_checks(hipStream_t s, const g2_prepared *gen, const g2_prepared *q1, const void *commitments48, const void *zs_le32, const void *ys_le32, const void *proofs48,
+               uint64_t count, uint8_t *result) {
+    dtmp<uint8_t> d_c(s), d_z(s), d_y(s), d_pi(s), d_st(s), d_ok(s); dtmp<g1j> d_p0(s), d_p1(s);
+    CHK(d_c.alloc(48 * count)); CHK(d_pi.alloc(48 * count)); CHK(d_z.alloc(32 * count)); CHK(d_y.alloc(32 * count));
+    CHK(d_st.alloc(count)); CHK(d_ok.alloc(count)); CHK(d_p0.alloc(count)); CHK(d_p1.alloc(count));
+    HIPCHK(hipMemcpyAsync(d_c.p, commitments48, 48 * count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_pi.p, proofs48, 48 * count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_z.p, zs_le32, 32 * count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_y.p, ys_le32, 32 * count, hipMemcpyHostToDevice, s));
+    launch_eth_check_inputs(s, d_c.p, d_z.p, d_y.p, d_pi.p, count, d_p0.p, d_p1.p, d_st.p);
+    // e(C - [y]G1 + [z] pi, G2) e(-pi, kzgSetupG2[1]) == 1  <=>  e(C - [y]G1, G2) == e(pi, [s - z]G2)  (eth/helpers.go:55-68)
+    launch_pairing_check(s, true, gen, q1, d_p0.p, d_p1.p, count, d_ok.p);
+    HIPCHK(hipGetLastError());
+    std::vector<uint8_t> st(count);
+    HIPCHK(hipMemcpyAsync(st.data(), d_st.p, count, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(result, d_ok.p, count, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint64_t i = 0; i < count; i++) if (st[i]) result[i] = st[i];
+    return KZG_HIP_OK;
+}
+
+// ---- batches by random linear combination per group of consecutive rows (verify_combine.hpp, k_verify_combine.hip) ----
+// From this many rows on the _combined entries combine by default (KZG_HIP_VERIFY_COMBINE = never / always forces a route): the smallest measured
+// count from which the combined route is faster on all-valid rows by more than the spread of the repeats.  Measured at 1 024 rows and up
+// (profiles/verify_combine.md): 7.7 .. 8.3 against 9.9 ms at 1 024 rows (one group), 12.3 against 66.2 ms at 65 536; below one full group nothing was measured.
+constexpr uint64_t COMBINE_FROM = 1024;
+constexpr uint64_t COMBINE_CHUNK_GROUPS = 1024;             // group checks per launch: the flat stretch of the wavefront pairing kernel
+constexpr uint64_t COMBINE_CHUNK_BYTES = 2048ull << 20;     // ... fewer when the groups' MSM workspaces would exceed this
+
+// what the last _combined call on this thread did (kzg_hip_test_combine_stats)
+struct combine_stats { uint64_t route, groups, failed, rechecked; };
+thread_local combine_stats t_combine;
+
+bool combine_route(uint64_t count) {
+    const knobs::combine_mode m = knobs::verify_combine();
+    return m == knobs::combine_mode::by_count ? count >= COMBINE_FROM : m == knobs::combine_mode::always;
+}
+uint64_t combine_rows() {
+    const uint64_t r = knobs::verify_combine_rows();
+    return !r ? VERIFY_COMBINE_ROWS : r > VERIFY_COMBINE_ROWS_MAX ? VERIFY_COMBINE_ROWS_MAX : r;
+}
+// groups of R rows one chunk of a call holds
+uint64_t combine_chunk_groups(uint64_t R) {
+    const uint64_t per = msm_workspace_bytes(classic_plan(combine_term_stride(R)), combine_term_stride(R), 1);
+    const uint64_t fit = COMBINE_CHUNK_BYTES / per;
+    return fit < 1 ? 1 : fit > COMBINE_CHUNK_GROUPS ? COMBINE_CHUNK_GROUPS : fit;
+}
+// the caller's seed, or 32 bytes from the operating system
+combine_seed combine_seed_of(const uint8_t *seed32) {
+    uint8_t buf[32];
+    if (!seed32) {
+        size_t got = 0;
+        while (got < sizeof buf) {
+            const ssize_t k = getrandom(buf + got, sizeof buf - got, 0);
+            if (k <= 0) break;
+            got += (size_t)k;
+        }
+        if (got < sizeof buf) {
+            std::random_device rd;
+            for (size_t i = 0; i < sizeof buf; i += 4) { const uint32_t v = rd(); memcpy(buf + i, &v, 4); }
+        }
+        seed32 = buf;
+    }
+    return combine_seed_from_bytes(seed32);
+}
+// A_g and B_g of the groups of `count` device-resident rows (rows row0 .. of the call): c / pi Kilic images (kilic) or device-internal ones,
+// x / y Montgomery images, status nullable.  d_a / d_b: combine_group_count(count, R) normalised points, Kilic images when to_kilic.
+int combine_group_sums(hipStream_t s, const combine_seed &seed, const g1j *d_c, const g1j *d_pi, bool kilic, const fr *d_x, const fr *d_y, const uint8_t *d_status,
+                       uint64_t row0, uint64_t count, uint64_t R, g1j *d_a, g1j *d_b, bool to_kilic) {
+    const uint64_t G = combine_group_count(count, R), stride = combine_term_stride(R), total = G * stride;
+    const msm_plan pb = classic_plan(stride), pa = classic_plan(R);
+    if (!msm_index_range_ok(pb, stride)) return KZG_HIP_ERR_TOO_WIDE;
+    dtmp<g1j> d_pts(s); dtmp<g1a> d_aff(s); dtmp<fr> d_sc(s); dtmp<uint8_t> d_ws(s);
+    CHK(d_pts.alloc(total)); CHK(d_aff.alloc(total)); CHK(d_sc.alloc(total)); CHK(d_ws.alloc(msm_workspace_bytes(pb, stride, G)));
+    prof_begin(s, "combine_scalars");
+    launch_combine_scalars(s, seed, d_x, d_y, d_status, row0, count, R, d_sc.p);
+    prof_end(s, "combine_scalars");
+    launch_combine_points(s, d_c, d_pi, count, R, kilic, d_pts.p);
+    if (kilic) launch_g1_from_kilic(s, d_pts.p, total);
+    launch_g1_to_affine(s, d_pts.p, d_aff.p, total);
+    prof_begin(s, "combine_msm");
+    launch_msm(s, pb, d_aff.p, d_sc.p, stride, stride, G, d_ws.p, d_b, to_kilic, stride, true);       // B_g: the whole slice
+    launch_msm(s, pa, d_aff.p + R, d_sc.p, stride, R, G, d_ws.p, d_a, to_kilic, stride, true);        // A_g: the proofs with the weights
+    prof_end(s, "combine_msm");
+    HIPCHK(hipGetLastError());
+    return KZG_HIP_OK;
+}
+// ok[g] = e(B_g, [1]G2) e(-A_g, [s]G2) == 1 over G groups, downloaded (the stream is synchronised)
+int combine_group_checks(hipStream_t s, const g2_prepared *gen, const g2_prepared *q1, const g1j *d_a, const g1j *d_b, uint64_t G, uint8_t *h_ok) {
+    dtmp<g1j> d_p1(s);
+    CHK(d_p1.alloc(G));
+    launch_combine_negate(s, d_a, G, d_p1.p);
+    return run_shared_check(s, gen, q1, d_b, d_p1.p, G, h_ok);
 }
 
 }  // namespace
@@ -335,25 +434,132 @@ int kzg_hip_eth_verify_kzg_proof_batch(kzg_hip_eth *eth, const void *commitments
     if (!count) return KZG_HIP_OK;
     if (!commitments48 || !zs_le32 || !ys_le32 || !proofs48 || !result) return KZG_HIP_ERR_BAD_ARG;
     stream_lease lease(eth->fs);
+    return eth_checks(lease.s, g->d_gen, g->d_s, commitments48, zs_le32, ys_le32, proofs48, count, result);
+    KZG_CATCH
+}
+
+// CheckProofSingle over `count` rows with one pairing check per group of rows (verify_combine.hpp); the rows of a failing group are re-checked one by one
+int kzg_hip_check_proof_single_batch_combined(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, uint64_t count,
+                                              const uint8_t *seed32, uint8_t *ok) {
+    if (!ks) return KZG_HIP_ERR_BAD_ARG;
+    KZG_TRY
+    const std::shared_ptr<g2_state> g = g2_of(ks->g2_mu, ks->g2);
+    if (!g) return KZG_HIP_ERR_BAD_ARG;
+    if (!count) return KZG_HIP_OK;
+    if (!commitments_g1 || !proofs_g1 || !xs_fr || !ys_fr || !ok) return KZG_HIP_ERR_BAD_ARG;
+    t_combine = combine_stats{};
+    stream_lease lease(ks->fs);
     hipStream_t s = lease.s;
-    dtmp<uint8_t> d_c(s), d_z(s), d_y(s), d_pi(s), d_st(s), d_ok(s); dtmp<g1j> d_p0(s), d_p1(s);
-    CHK(d_c.alloc(48 * count)); CHK(d_pi.alloc(48 * count)); CHK(d_z.alloc(32 * count)); CHK(d_y.alloc(32 * count));
-    CHK(d_st.alloc(count)); CHK(d_ok.alloc(count)); CHK(d_p0.alloc(count)); CHK(d_p1.alloc(count));
-    HIPCHK(hipMemcpyAsync(d_c.p, commitments48, 48 * count, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_pi.p, proofs48, 48 * count, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_z.p, zs_le32, 32 * count, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_y.p, ys_le32, 32 * count, hipMemcpyHostToDevice, s));
-    launch_eth_check_inputs(s, d_c.p, d_z.p, d_y.p, d_pi.p, count, d_p0.p, d_p1.p, d_st.p);
-    // e(C - [y]G1 + [z] pi, G2) e(-pi, kzgSetupG2[1]) == 1  <=>  e(C - [y]G1, G2) == e(pi, [s - z]G2)  (eth/helpers.go:55-68)
-    launch_pairing_check(s, true, g->d_gen, g->d_s, d_p0.p, d_p1.p, count, d_ok.p);
-    HIPCHK(hipGetLastError());
-    std::vector<uint8_t> st(count);
-    HIPCHK(hipMemcpyAsync(st.data(), d_st.p, count, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(result, d_ok.p, count, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (uint64_t i = 0; i < count; i++) if (st[i]) result[i] = st[i];
+    if (!combine_route(count)) return kzg_checks(s, g->d_gen, g->d_s, commitments_g1, proofs_g1, ys_fr, nullptr, xs_fr, nullptr, count, ok);
+    t_combine.route = 1;
+    const combine_seed seed = combine_seed_of(seed32);
+    const uint64_t R = combine_rows(), chunk = combine_chunk_groups(R) * R;
+    const g1j *c = (const g1j *)commitments_g1, *pi = (const g1j *)proofs_g1; const fr *xs = (const fr *)xs_fr, *ys = (const fr *)ys_fr;
+    std::vector<uint8_t> gok;
+    for (uint64_t i0 = 0; i0 < count; i0 += chunk) {
+        const uint64_t k = count - i0 < chunk ? count - i0 : chunk, G = combine_group_count(k, R);
+        {
+            dtmp<g1j> d_c(s), d_pi(s), d_a(s), d_b(s); dtmp<fr> d_x(s), d_y(s);
+            CHK(d_c.alloc(k)); CHK(d_pi.alloc(k)); CHK(d_x.alloc(k)); CHK(d_y.alloc(k)); CHK(d_a.alloc(G)); CHK(d_b.alloc(G));
+            HIPCHK(hipMemcpyAsync(d_c.p, c + i0, k * sizeof(g1j), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_pi.p, pi + i0, k * sizeof(g1j), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_x.p, xs + i0, k * sizeof(fr), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_y.p, ys + i0, k * sizeof(fr), hipMemcpyHostToDevice, s));
+            CHK(combine_group_sums(s, seed, d_c.p, d_pi.p, true, d_x.p, d_y.p, nullptr, i0, k, R, d_a.p, d_b.p, false));
+            gok.assign(G, 0);
+            CHK(combine_group_checks(s, g->d_gen, g->d_s, d_a.p, d_b.p, G, gok.data()));
+        }
+        t_combine.groups += G;
+        for (uint64_t gi = 0; gi < G; gi++) {
+            const uint64_t b = i0 + combine_group_begin(gi, R), e = i0 + combine_group_end(gi, R, k);
+            if (gok[gi]) { memset(ok + b, 1, e - b); continue; }
+            t_combine.failed++; t_combine.rechecked += e - b;
+            CHK(kzg_checks(s, g->d_gen, g->d_s, c + b, pi + b, ys + b, nullptr, xs + b, nullptr, e - b, ok + b));
+        }
+    }
     return KZG_HIP_OK;
     KZG_CATCH
+}
+
+// eth.VerifyKZGProof over `count` rows of bytes likewise: rows with status 2 or 3 keep that byte and drop out of their group's combination
+int kzg_hip_eth_verify_kzg_proof_batch_combined(kzg_hip_eth *eth, const void *commitments48, const void *zs_le32, const void *ys_le32, const void *proofs48,
+                                                uint64_t count, const uint8_t *seed32, uint8_t *result) {
+    if (!eth) return KZG_HIP_ERR_BAD_ARG;
+    KZG_TRY
+    const std::shared_ptr<g2_state> g = g2_of(eth->g2_mu, eth->g2);
+    if (!g) return KZG_HIP_ERR_BAD_ARG;
+    if (!count) return KZG_HIP_OK;
+    if (!commitments48 || !zs_le32 || !ys_le32 || !proofs48 || !result) return KZG_HIP_ERR_BAD_ARG;
+    t_combine = combine_stats{};
+    stream_lease lease(eth->fs);
+    hipStream_t s = lease.s;
+    if (!combine_route(count)) return eth_checks(s, g->d_gen, g->d_s, commitments48, zs_le32, ys_le32, proofs48, count, result);
+    t_combine.route = 1;
+    const combine_seed seed = combine_seed_of(seed32);
+    const uint64_t R = combine_rows(), chunk = combine_chunk_groups(R) * R;
+    const uint8_t *c48 = (const uint8_t *)commitments48, *pi48 = (const uint8_t *)proofs48, *zs = (const uint8_t *)zs_le32, *ys = (const uint8_t *)ys_le32;
+    std::vector<uint8_t> gok, st;
+    for (uint64_t i0 = 0; i0 < count; i0 += chunk) {
+        const uint64_t k = count - i0 < chunk ? count - i0 : chunk, G = combine_group_count(k, R);
+        {
+            dtmp<uint8_t> d_c48(s), d_pi48(s), d_z32(s), d_y32(s), d_cbad(s), d_pbad(s), d_st(s); dtmp<g1j> d_c(s), d_pi(s), d_a(s), d_b(s); dtmp<fr> d_z(s), d_y(s);
+            CHK(d_c48.alloc(48 * k)); CHK(d_pi48.alloc(48 * k)); CHK(d_z32.alloc(32 * k)); CHK(d_y32.alloc(32 * k)); CHK(d_cbad.alloc(k)); CHK(d_pbad.alloc(k));
+            CHK(d_st.alloc(k)); CHK(d_c.alloc(k)); CHK(d_pi.alloc(k)); CHK(d_z.alloc(k)); CHK(d_y.alloc(k)); CHK(d_a.alloc(G)); CHK(d_b.alloc(G));
+            HIPCHK(hipMemcpyAsync(d_c48.p, c48 + 48 * i0, 48 * k, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_pi48.p, pi48 + 48 * i0, 48 * k, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_z32.p, zs + 32 * i0, 32 * k, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_y32.p, ys + 32 * i0, 32 * k, hipMemcpyHostToDevice, s));
+            launch_g1_decompress_rows(s, d_c48.p, d_c.p, k, d_cbad.p, false);
+            launch_g1_decompress_rows(s, d_pi48.p, d_pi.p, k, d_pbad.p, false);
+            launch_eth_combine_fields(s, d_z32.p, d_y32.p, d_cbad.p, d_pbad.p, k, d_z.p, d_y.p, d_st.p);
+            CHK(combine_group_sums(s, seed, d_c.p, d_pi.p, false, d_z.p, d_y.p, d_st.p, i0, k, R, d_a.p, d_b.p, false));
+            drain_on_exit drain(s);                                                              // (an error below leaves no copy into st in flight)
+            st.assign(k, 0); gok.assign(G, 0);
+            HIPCHK(hipMemcpyAsync(st.data(), d_st.p, k, hipMemcpyDeviceToHost, s));
+            CHK(combine_group_checks(s, g->d_gen, g->d_s, d_a.p, d_b.p, G, gok.data()));
+        }
+        memcpy(result + i0, st.data(), k);                                                       // the statuses first: 0 where the row's inputs are valid
+        t_combine.groups += G;
+        for (uint64_t gi = 0; gi < G; gi++) {
+            const uint64_t b = i0 + combine_group_begin(gi, R), e = i0 + combine_group_end(gi, R, k);
+            if (gok[gi]) { for (uint64_t i = b; i < e; i++) if (!result[i]) result[i] = 1; continue; }
+            t_combine.failed++; t_combine.rechecked += e - b;
+            CHK(eth_checks(s, g->d_gen, g->d_s, c48 + 48 * b, zs + 32 * b, ys + 32 * b, pi48 + 48 * b, e - b, result + b));
+        }
+    }
+    return KZG_HIP_OK;
+    KZG_CATCH
+}
+
+// test hooks (kzg_hip_internal.h): A_g and B_g of every group as normalised Kilic images, and what the calling thread's last _combined call did
+int kzg_hip_test_combine_points(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, uint64_t count,
+                                const uint8_t *seed32, void *out_a_g1, void *out_b_g1) {
+    if (!ks || !seed32 || (count && (!commitments_g1 || !proofs_g1 || !xs_fr || !ys_fr || !out_a_g1 || !out_b_g1))) return KZG_HIP_ERR_BAD_ARG;
+    if (!count) return KZG_HIP_OK;
+    KZG_TRY
+    stream_lease lease(ks->fs);
+    hipStream_t s = lease.s;
+    const combine_seed seed = combine_seed_of(seed32);
+    const uint64_t R = combine_rows(), G = combine_group_count(count, R);
+    if (G > COMBINE_CHUNK_GROUPS || G > combine_chunk_groups(R)) return KZG_HIP_ERR_TOO_WIDE;
+    dtmp<g1j> d_c(s), d_pi(s), d_a(s), d_b(s); dtmp<fr> d_x(s), d_y(s);
+    CHK(d_c.alloc(count)); CHK(d_pi.alloc(count)); CHK(d_x.alloc(count)); CHK(d_y.alloc(count)); CHK(d_a.alloc(G)); CHK(d_b.alloc(G));
+    HIPCHK(hipMemcpyAsync(d_c.p, commitments_g1, count * sizeof(g1j), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_pi.p, proofs_g1, count * sizeof(g1j), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_x.p, xs_fr, count * sizeof(fr), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_y.p, ys_fr, count * sizeof(fr), hipMemcpyHostToDevice, s));
+    CHK(combine_group_sums(s, seed, d_c.p, d_pi.p, true, d_x.p, d_y.p, nullptr, 0, count, R, d_a.p, d_b.p, true));
+    HIPCHK(hipMemcpyAsync(out_a_g1, d_a.p, G * sizeof(g1j), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_b_g1, d_b.p, G * sizeof(g1j), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return KZG_HIP_OK;
+    KZG_CATCH
+}
+int kzg_hip_test_combine_stats(uint64_t out[6]) {
+    if (!out) return KZG_HIP_ERR_BAD_ARG;
+    out[0] = t_combine.route; out[1] = t_combine.groups; out[2] = t_combine.failed; out[3] = t_combine.rechecked;
+    out[4] = COMBINE_FROM; out[5] = combine_rows();
+    return KZG_HIP_OK;
 }
 
 // eth.VerifyAggregateKZGProof (eth/eth.go:155-172) over many sidecars.  Per chunk of whole sidecars: ONE upload of the raw bytes, then

@@ -142,9 +142,11 @@ struct msm_plan {
 inline bool msm_index_range_ok(const msm_plan &p, uint64_t n) { return n < (1ull << 27) && 2 * p.table_n < (1ull << 30); }
 size_t msm_workspace_bytes(const msm_plan &p, uint64_t n, uint64_t batch);
 // batch MSMs over the same affine points, scalars in rows of sc_stride: out[b] = sum_i scalars[b][i] * P_i, NORMALISED (Z = one),
-// as Kilic images when to_kilic
+// as Kilic images when to_kilic.  table_stride != 0 (plans with 16 window groups): blob b reads its own slice of points, table + b * table_stride.
+// crowded_buckets: the caller knows that a few buckets hold a large share of every blob's entries (many scalars of 128 bits: their second GLV half
+// is 0 .. 3), so the balanced accumulate (a lane per 64 sorted entries) is taken as soon as fewer than 8 lanes would share a bucket
 void launch_msm(hipStream_t s, const msm_plan &p, const g1a *table, const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, void *workspace, g1j *out,
-                bool to_kilic);
+                bool to_kilic, uint64_t table_stride = 0, bool crowded_buckets = false);
 // fixed-base window table: out[w * n + i] = 2^(c w) * pts[i], affine
 void launch_msm_window_table(hipStream_t s, const g1a *pts, uint64_t n, uint32_t c, uint32_t nwin, g1j *tmp, g1a *out);
 
@@ -238,6 +240,19 @@ void launch_eth_merge_status(hipStream_t s, const uint8_t *status, const uint8_t
 // result[j] = 1 when every flag of off[j] .. off[j + 1] (blocks + 1 entries) is set, else 4
 void launch_eth_tx_hashes_check(hipStream_t s, const uint8_t *c48, const uint8_t *want32, const uint64_t *off, uint64_t total, uint64_t blocks, uint8_t *match,
                                 uint8_t *result);
+
+// ---------------- k_verify_combine.hip ----------------
+// batches of KZG checks by random linear combination per group of R consecutive rows (lane bodies and the layout of a group's terms:
+// verify_combine.hpp).  sc / out: combine_group_count(count, R) slices of combine_term_stride(R) slots
+struct combine_seed;
+// term scalars (Montgomery) of rows row0 .. row0 + count of the call from their x and y (Montgomery); status (nullable): non-zero rows get weight 0
+void launch_combine_scalars(hipStream_t s, const combine_seed &seed, const fr *xs, const fr *ys, const uint8_t *status, uint64_t row0, uint64_t count, uint64_t R, fr *sc);
+// term points as they came in (Kilic images when kilic, else device-internal), the generator in the same form
+void launch_combine_points(hipStream_t s, const g1j *c, const g1j *pi, uint64_t count, uint64_t R, bool kilic, g1j *out);
+void launch_combine_negate(hipStream_t s, const g1j *a, uint64_t n, g1j *out);   // out[g] = -a[g]
+// eth form: z, y as Montgomery images and status 0 / 2 / 3 per row from the bytes and the decompression flags of commitment and proof
+void launch_eth_combine_fields(hipStream_t s, const uint8_t *zs, const uint8_t *ys, const uint8_t *c_bad, const uint8_t *pi_bad, uint64_t n, fr *z_out, fr *y_out,
+                               uint8_t *status);
 
 // profiling hook (HIP events around the dominant kernel), see capi.hip
 void prof_begin(hipStream_t s, const char *name);

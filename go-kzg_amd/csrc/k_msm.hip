@@ -163,7 +163,7 @@ __global__ __launch_bounds__(MSM_SORT_T) void k_msm_sort(uint32_t ngroups, uint6
 }
 
 // S lanes per (blob, bucket): each walks its share of the bucket's sorted list, then the S partial sums are merged through LDS
-__global__ __launch_bounds__(MSM_ACC_BLOCK, 2) void k_msm_accumulate(const g1a *table, uint8_t *ws, size_t per_blob, size_t entries_off, size_t offsets_off,
+__global__ __launch_bounds__(MSM_ACC_BLOCK, 2) void k_msm_accumulate(const g1a *table, uint64_t table_stride, uint8_t *ws, size_t per_blob, size_t entries_off, size_t offsets_off,
                                                                   size_t buckets_off, uint32_t K, uint32_t S, uint64_t total) {
     __shared__ fb_partial buf[MSM_ACC_BLOCK];
     const uint32_t tid = threadIdx.x;
@@ -177,6 +177,7 @@ __global__ __launch_bounds__(MSM_ACC_BLOCK, 2) void k_msm_accumulate(const g1a *
         const uint32_t *entries = (const uint32_t *)(ws + b * per_blob + entries_off);
         const uint32_t *offsets = (const uint32_t *)(ws + b * per_blob + offsets_off);
         const uint32_t s0 = offsets[2 * key], len = offsets[2 * key + 2] - s0;
+        table += b * table_stride;                         // the blob's own slice of points (0: all blobs share one table)
         const uint32_t s = s0 + (uint32_t)((uint64_t)len * sidx / S), e = s0 + (uint32_t)((uint64_t)len * (sidx + 1) / S);
 #pragma nounroll
         for (uint32_t i = s; i < e; i++) {
@@ -210,11 +211,12 @@ __global__ __launch_bounds__(MSM_ACC_BLOCK, 2) void k_msm_accumulate(const g1a *
 // slots and k_msm_merge_segs adds them up per bucket (on average one addition per bucket).  Inside a bucket the phi half comes first (k_msm_sort):
 // it is accumulated un-mapped and phi -- X <- beta X on the XYZZ sum -- is applied once, when the walk crosses into the plain half or leaves the bucket.
 __device__ __forceinline__ void acc_apply_phi(g1x_acc &a) { if (!a.inf) a.v.x = mulq(a.v.x, unpackq(glv_beta())); }
-__global__ __launch_bounds__(MSM_ACC_BLOCK, 2) void k_msm_accumulate_seg(const g1a *table, uint8_t *ws, size_t per_blob, size_t entries_off, size_t offsets_off,
+__global__ __launch_bounds__(MSM_ACC_BLOCK, 2) void k_msm_accumulate_seg(const g1a *table, uint64_t table_stride, uint8_t *ws, size_t per_blob, size_t entries_off, size_t offsets_off,
                                                                       size_t buckets_off, size_t segs_off, uint32_t K2, uint64_t nseg, uint64_t total) {
     const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (t >= total) return;
     const uint64_t b = t / nseg; const uint32_t seg = (uint32_t)(t % nseg);
+    table += b * table_stride;
     const uint32_t *entries = (const uint32_t *)(ws + b * per_blob + entries_off);
     const uint32_t *offsets = (const uint32_t *)(ws + b * per_blob + offsets_off);
     fb_partial *buckets = (fb_partial *)(ws + b * per_blob + buckets_off);
@@ -412,7 +414,7 @@ __global__ __launch_bounds__(256) void k_msm_combine(uint8_t *ws, size_t per_blo
 }
 
 void launch_msm(hipStream_t s, const msm_plan &p, const g1a *table, const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, void *workspace, g1j *out,
-                bool to_kilic) {
+                bool to_kilic, uint64_t table_stride, bool crowded_buckets) {
     if (!batch) return;
     msm_ws_layout L = ws_layout(p, n);
     uint8_t *ws = (uint8_t *)workspace;
@@ -429,15 +431,18 @@ void launch_msm(hipStream_t s, const msm_plan &p, const g1a *table, const fr *sc
     prof_begin(s, "msm_accumulate");
     // from one full round of resident lanes on (64 MSMs of 4096 points): measured 2.19 vs 2.98 ms at 64, 12.3 vs 17.3 ms at 512; below, the S-lanes-per-bucket
     // form wins (32: 1.89 vs 2.07 ms, 8: 1.14 vs 1.47 ms: its lanes are shorter and a lone MSM is latency-bound)
-    const bool balanced = seg_mode == 1 || (seg_mode < 0 && batch * L.nseg >= 2 * device_simd_lanes());
+    // crowded_buckets (the combined proof checks: 128-bit weights have a GLV half of 0 .. 3, so a third of a blob's entries sit in three buckets and a lane per
+    // bucket walks hundreds of them in a row): also from the batch at which a bucket's list is shared by fewer than 8 lanes (65 536 rows in 64 MSMs: 27 ms per
+    // launch with a lane per bucket, 1.5 ms balanced; profiles/verify_combine.md)
+    const bool balanced = seg_mode == 1 || (seg_mode < 0 && (batch * L.nseg >= 2 * device_simd_lanes() || (crowded_buckets && S < 8)));
     if (balanced) {
         const uint64_t tseg = batch * L.nseg, tb = batch * L.K;
-        hipLaunchKernelGGL(k_msm_accumulate_seg, dim3((uint32_t)((tseg + MSM_ACC_BLOCK - 1) / MSM_ACC_BLOCK)), dim3(MSM_ACC_BLOCK), 0, s, table, ws, L.per_blob,
+        hipLaunchKernelGGL(k_msm_accumulate_seg, dim3((uint32_t)((tseg + MSM_ACC_BLOCK - 1) / MSM_ACC_BLOCK)), dim3(MSM_ACC_BLOCK), 0, s, table, table_stride, ws, L.per_blob,
                            L.entries_off, L.offsets_off, L.buckets_off, L.segs_off, K2, L.nseg, tseg);
         hipLaunchKernelGGL(k_msm_merge_segs, dim3((uint32_t)((tb + MSM_ACC_BLOCK - 1) / MSM_ACC_BLOCK)), dim3(MSM_ACC_BLOCK), 0, s, ws, L.per_blob, L.offsets_off,
                            L.buckets_off, L.segs_off, K, tb);
     } else
-        hipLaunchKernelGGL(k_msm_accumulate, dim3((uint32_t)((total + MSM_ACC_BLOCK - 1) / MSM_ACC_BLOCK)), dim3(MSM_ACC_BLOCK), 0, s, table, ws, L.per_blob,
+        hipLaunchKernelGGL(k_msm_accumulate, dim3((uint32_t)((total + MSM_ACC_BLOCK - 1) / MSM_ACC_BLOCK)), dim3(MSM_ACC_BLOCK), 0, s, table, table_stride, ws, L.per_blob,
                            L.entries_off, L.offsets_off, L.buckets_off, K, S, total);
     prof_end(s, "msm_accumulate");
     const knobs::msm_reduce_mode reduce_mode = knobs::msm_reduce();   // tests / A/B runs: force a form at any batch size

@@ -68,6 +68,17 @@ int kzg_hip_test_wave_fp12_op(kzg_hip_fft *fs, int op, const void *a, const void
  * out[0] = 1 one wavefront per check, 0 one lane per check; out[1] = the count below which the wavefront kernel is the default */
 int kzg_hip_test_pairing_route(uint64_t n, uint64_t out[2]);
 
+/* test hooks of the _combined proof checks (capi_verify.hip, verify_combine.hpp).
+ * kzg_hip_test_combine_points: A_g = sum r_i pi_i and B_g = sum r_i C_i + sum (r_i x_i) pi_i - (sum r_i y_i) G1 of every group of
+ * KZG_HIP_VERIFY_COMBINE_ROWS consecutive rows, for the inputs of kzg_hip_check_proof_single_batch_combined and a seed (not NULL), as normalised
+ * Kilic images (infinity (0, R, 0)): ceil(count / rows) points each.  KZG_HIP_ERR_TOO_WIDE for more groups than one launch holds.
+ * kzg_hip_test_combine_stats: what the calling thread's last _combined call did -- out[0] = 1 the combination ran, 0 the per-row path; out[1] = group
+ * checks made; out[2] = groups that failed; out[3] = rows re-checked one by one; and the routing now: out[4] = the count from which the default
+ * combines, out[5] = rows per group */
+int kzg_hip_test_combine_points(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, uint64_t count,
+                                const uint8_t *seed32, void *out_a_g1, void *out_b_g1);
+int kzg_hip_test_combine_stats(uint64_t out[6]);
+
 /* test hook of the G2 half of a setup (capi_verify.hip): how many times the handle built its fixed-base table of bls.GenG2 -- 0 before the first
  * kzg_hip_g2_mul_generator_vec / kzg_hip_generate_testing_setup_g2, 1 ever after, however many threads made the first call at once */
 int kzg_hip_test_g2_table_builds(kzg_hip_fft *fs, uint64_t *builds);

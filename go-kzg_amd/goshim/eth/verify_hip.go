@@ -69,6 +69,51 @@ func VerifyKZGProofBatch(commitments []KZGCommitment, zs, ys [][32]byte, proofs 
 	return oks, errs
 }
 
+// VerifyKZGProofBatchCombined: what VerifyKZGProofBatch returns, with one pairing check per group of rows (a random linear combination per group; rows
+// with invalid inputs drop out of it, the rows of a failing group are re-checked one by one).  seed: nil draws the weights' seed from the operating
+// system; 32 bytes make a run reproducible -- a seed the prover can know in advance voids the 2^-128 bound.
+func VerifyKZGProofBatchCombined(commitments []KZGCommitment, zs, ys [][32]byte, proofs []KZGProof, seed *[32]byte) ([]bool, []error) {
+	n := len(commitments)
+	if len(zs) != n || len(ys) != n || len(proofs) != n {
+		panic("VerifyKZGProofBatchCombined: slices of different lengths")
+	}
+	oks, errs := make([]bool, n), make([]error, n)
+	if n == 0 {
+		return oks, errs
+	}
+	hipSetupG2Mu.Lock()
+	if hipSetupG2For != hipEth {
+		if st := C.kzg_hip_eth_set_setup_g2(hipEth, unsafe.Pointer(&kzgSetupG2[0]), C.uint64_t(len(kzgSetupG2))); st != C.KZG_HIP_OK {
+			hipSetupG2Mu.Unlock()
+			panic("kzg_hip: eth_set_setup_g2 failed")
+		}
+		hipSetupG2For = hipEth
+	}
+	hipSetupG2Mu.Unlock()
+	var sp *C.uint8_t
+	if seed != nil {
+		sp = (*C.uint8_t)(unsafe.Pointer(&seed[0]))
+	}
+	res := make([]uint8, n)
+	if st := C.kzg_hip_eth_verify_kzg_proof_batch_combined(hipEth, unsafe.Pointer(&commitments[0]), unsafe.Pointer(&zs[0]), unsafe.Pointer(&ys[0]),
+		unsafe.Pointer(&proofs[0]), C.uint64_t(n), sp, (*C.uint8_t)(unsafe.Pointer(&res[0]))); st != C.KZG_HIP_OK {
+		panic("kzg_hip: eth_verify_kzg_proof_batch_combined failed")
+	}
+	for i, r := range res {
+		switch r {
+		case 1:
+			oks[i] = true
+		case 2, 3:
+			// invalid inputs (the cold path): the reference's own parsing on the CPU names the input and the cause, with its error texts
+			_, errs[i] = VerifyKZGProof(commitments[i], zs[i], ys[i], proofs[i])
+			if errs[i] == nil {
+				panic("kzg_hip: eth_verify_kzg_proof_batch_combined rejected inputs that VerifyKZGProof accepts")
+			}
+		}
+	}
+	return oks, errs
+}
+
 // VerifyAggregateKZGProofBatch: (ok[j], errs[j]) = VerifyAggregateKZGProof(blobs[j], expectedKZGCommitments[j], proofs[j]) (eth/eth.go:155-172)
 // for many blocks in one device call: transcripts, aggregation, evaluation and the pairing all run there.  A block without blobs is valid input.
 func VerifyAggregateKZGProofBatch(blobs []BlobSequence, expectedKZGCommitments []KZGCommitmentSequence, proofs []KZGProof) ([]bool, []error) {

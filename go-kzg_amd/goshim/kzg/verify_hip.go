@@ -60,6 +60,28 @@ func (ks *KZGSettings) CheckProofSingleBatch(commitments, proofs []bls.G1Point, 
 	return okMask(ok)
 }
 
+// CheckProofSingleBatchCombined: the mask of CheckProofSingleBatch with one pairing check per group of rows (a random linear combination per group;
+// the rows of a failing group are re-checked one by one).  seed: nil draws the weights' seed from the operating system; 32 bytes make a run
+// reproducible -- a seed the prover can know in advance voids the 2^-128 bound.  Presupposes points of G1, as CheckProofSingle does.
+func (ks *KZGSettings) CheckProofSingleBatchCombined(commitments, proofs []bls.G1Point, xs, ys []bls.Fr, seed *[32]byte) []bool {
+	defer runtime.KeepAlive(ks)
+	n := len(commitments)
+	if len(proofs) != n || len(xs) != n || len(ys) != n {
+		panic("CheckProofSingleBatchCombined: slices of different lengths")
+	}
+	if n == 0 {
+		return nil
+	}
+	var sp *C.uint8_t
+	if seed != nil {
+		sp = (*C.uint8_t)(unsafe.Pointer(&seed[0]))
+	}
+	ok := make([]uint8, n)
+	hipMust(C.kzg_hip_check_proof_single_batch_combined(ks.hipSecretG2(), g1Ptr(commitments), g1Ptr(proofs), frPtr(xs), frPtr(ys), C.uint64_t(n), sp,
+		(*C.uint8_t)(unsafe.Pointer(&ok[0]))))
+	return okMask(ok)
+}
+
 // CheckProofMultiBatch: out[i] = ks.CheckProofMulti(commitments[i], proofs[i], xs[i], ys[i]); every ys[i] has the same length.
 func (ks *KZGSettings) CheckProofMultiBatch(commitments, proofs []bls.G1Point, xs []bls.Fr, ys [][]bls.Fr) []bool {
 	defer runtime.KeepAlive(ks)

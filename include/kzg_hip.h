@@ -281,6 +281,25 @@ int kzg_hip_eth_set_setup_g2(kzg_hip_eth *eth, const void *setup_g2, uint64_t n)
  * 2 z or y not below r ("invalid evaluation point" / "invalid expected output"), 3 commitment or proof not a valid G1 encoding */
 int kzg_hip_eth_verify_kzg_proof_batch(kzg_hip_eth *eth, const void *commitments48, const void *zs_le32, const void *ys_le32, const void *proofs48, uint64_t count,
                                        uint8_t *result);
+/* The two batch checks above with ONE pairing check per group of consecutive rows instead of one per row, for callers whose batches are almost
+ * always valid throughout.  Arguments, error codes and output bytes are those of the per-row entries.  Per group g of rows i the library draws
+ * 128-bit weights r_i and checks e(B_g, [1]G2) e(-A_g, [s]G2) == 1 with A_g = sum r_i pi_i and B_g = sum r_i C_i + sum (r_i x_i) pi_i - (sum r_i y_i) G1
+ * (two multi-scalar multiplications per group).  If every row of a group is valid the group passes and its rows get 1; the rows of a group that
+ * fails are re-checked one by one by the per-row path, so the answer is the per-row mask.  A group that contains an invalid row passes with
+ * probability at most 2^-128 over the weights, for points of G1.
+ * Weights: r_i = the little-endian integer of the first 16 bytes of SHA-256(seed32 | "KZGHIPRC" | le64(i)), i the row's index in the call.
+ * seed32 == NULL: the library draws 32 bytes from the operating system for the call (getrandom, else std::random_device).  A non-NULL seed is for
+ * reproducible runs and tests: A SEED THAT THE PROVER CAN KNOW BEFORE IT CHOOSES ITS PROOFS VOIDS THE BOUND (invalid rows whose errors cancel
+ * under known weights pass).
+ * kzg_hip_check_proof_single_batch_combined takes Kilic images and PRESUPPOSES POINTS OF G1, as the reference's CheckProofSingle does: it checks
+ * neither the curve equation nor the subgroup.  kzg_hip_eth_verify_kzg_proof_batch_combined decodes and subgroup-checks every point; rows with
+ * result 2 or 3 keep that byte and drop out of their group's combination (weight 0), so their neighbours still pass in one group check.
+ * Groups hold KZG_HIP_VERIFY_COMBINE_ROWS rows (default 1024).  KZG_HIP_VERIFY_COMBINE=never|always forces the per-row path or the combination;
+ * by default small batches take the per-row path (README, "Environment knobs").  Both switches are read per call. */
+int kzg_hip_check_proof_single_batch_combined(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr,
+                                              uint64_t count, const uint8_t *seed32, uint8_t *ok);
+int kzg_hip_eth_verify_kzg_proof_batch_combined(kzg_hip_eth *eth, const void *commitments48, const void *zs_le32, const void *ys_le32, const void *proofs48,
+                                                uint64_t count, const uint8_t *seed32, uint8_t *result);
 /* eth.VerifyAggregateKZGProof (eth/eth.go:155-172) over `sidecars` blocks.  blob_counts[j] blobs belong to block j (0 is valid); blobs_le32 holds
  * all blobs in block order (sum(blob_counts) x n x 32 little-endian bytes), commitments48 the expected commitments in the same order, proofs48 one
  * aggregated proof per block.  result[j]: 1 valid, 0 the pairing check failed, 2 a field element of one of the block's blobs is >= r ("could not
