@@ -103,6 +103,8 @@ def lib():
         "kzg_hip_check_proof_single_batch_combined": (i32, [vp, vp, vp, vp, vp, u64, vp, vp]),
         "kzg_hip_eth_verify_kzg_proof_batch_combined": (i32, [vp, vp, vp, vp, vp, u64, vp, vp]),
         "kzg_hip_test_combine_points": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, vp]), "kzg_hip_test_combine_stats": (i32, [C.POINTER(u64)]),
+        "kzg_hip_check_proof_multi_batch_combined": (i32, [vp, vp, vp, vp, vp, u64, u64, vp, vp]),
+        "kzg_hip_test_combine_multi_points": (i32, [vp, vp, vp, vp, vp, u64, u64, vp, vp, vp, vp]), "kzg_hip_test_combine_multi_route": (i32, [u64, u64, C.POINTER(u64)]),
         "kzg_hip_eth_set_setup_g2": (i32, [vp, vp, u64]), "kzg_hip_eth_verify_kzg_proof_batch": (i32, [vp, vp, vp, vp, vp, u64, vp]),
         "kzg_hip_eth_verify_aggregate_kzg_proof_batch": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]),
         "kzg_hip_eth_kzg_to_versioned_hash_batch": (i32, [vp, vp, u64, vp]), "kzg_hip_eth_kzg_to_versioned_hash_batch_dev": (i32, [vp, vp, u64, vp]),
@@ -258,6 +260,14 @@ def combine_stats():
     _chk(lib().kzg_hip_test_combine_stats(out))
     return {"route": "combined" if out[0] else "per_row", "groups": int(out[1]), "failed": int(out[2]), "rechecked": int(out[3]),
             "combine_from": int(out[4]), "rows": int(out[5])}
+
+
+def combine_multi_route(n, count):
+    """test hook: ("combined" | "per_row", COMBINE_MULTI_FROM): the route of check_proof_multi_batch_combined for `count` rows of n values under
+    the current environment"""
+    out = (C.c_uint64 * 2)()
+    _chk(lib().kzg_hip_test_combine_multi_route(n, count, out))
+    return ("combined" if out[0] else "per_row"), int(out[1])
 
 
 def pairing_route(n):
@@ -786,6 +796,37 @@ class KZGSettings:
         ok = np.zeros(count, dtype=np.uint8)
         _chk(lib().kzg_hip_check_proof_multi_batch(self.h, _p(c), _p(pi), _p(xs), _p(ys), ys.shape[1], count, _p(ok)))
         return ok.astype(bool)
+
+    def _multi_rows(self, commitments, proofs, xs, ys):
+        c, pi, xs = _g1(commitments), _g1(proofs), _fr(xs)
+        count = c.shape[0]
+        ys = np.ascontiguousarray(ys, dtype=np.uint64)
+        ys = ys if ys.ndim == 3 else ys.reshape(count, -1, 4)
+        if ys.shape[0] != count or ys.shape[2] != 4:
+            raise KzgError(ERR_LEN_MISMATCH, "one row of ys per check")
+        if not (pi.shape[0] == xs.shape[0] == count):
+            raise KzgError(ERR_LEN_MISMATCH, "one commitment, proof and x per check")
+        return c, pi, xs, ys, count
+
+    def check_proof_multi_batch_combined(self, commitments, proofs, xs, ys, seed=None):
+        """the same mask with one pairing check per group of rows (kzg_hip_check_proof_multi_batch_combined): what a DAS sampler runs on coset
+        proofs.  The rows of a failing group are re-checked one by one; no commitment table is built.  seed as check_proof_single_batch_combined.
+        Presupposes points of G1, as CheckProofMulti does"""
+        c, pi, xs, ys, count = self._multi_rows(commitments, proofs, xs, ys)
+        ok = np.zeros(count, dtype=np.uint8)
+        _chk(lib().kzg_hip_check_proof_multi_batch_combined(self.h, _p(c), _p(pi), _p(xs), _p(ys), ys.shape[1], count, _seed32(seed), _p(ok)))
+        return ok.astype(bool)
+
+    def test_combine_multi_points(self, commitments, proofs, xs, ys, seed):
+        """test hook: (A_g, B_g, J_g) of every group of the combined multi check for these inputs and this seed: normalised images, and
+        (groups, np, 4) Montgomery values"""
+        c, pi, xs, ys, count = self._multi_rows(commitments, proofs, xs, ys)
+        groups = -(-count // combine_stats()["rows"])
+        n = ys.shape[1]
+        npad = 1 if n <= 1 else 1 << (n - 1).bit_length()
+        a, b, j = g1_empty(groups), g1_empty(groups), np.zeros((groups, npad, 4), dtype=np.uint64)
+        _chk(lib().kzg_hip_test_combine_multi_points(self.h, _p(c), _p(pi), _p(xs), _p(ys), n, count, _seed32(seed), _p(a), _p(b), _p(j)))
+        return a, b, j
 
     def toeplitz_part2(self, toeplitz_coeffs, x_ext_fft):
         toeplitz_coeffs, x_ext_fft = _fr(toeplitz_coeffs), _g1(x_ext_fft)

@@ -4,7 +4,7 @@
 #include "capi_common.hpp"
 #include "pairing.hpp"
 #include "sha256_lane.hpp"
-#include "verify_combine.hpp"
+#include "verify_combine_multi.hpp"
 #include <random>
 #include <sys/random.h>
 
@@ -208,22 +208,34 @@ combine_seed combine_seed_of(const uint8_t *seed32) {
 }
 // A_g and B_g of the groups of `count` device-resident rows (rows row0 .. of the call): c / pi Kilic images (kilic) or device-internal ones,
 // x / y Montgomery images, status nullable.  d_a / d_b: combine_group_count(count, R) normalised points, Kilic images when to_kilic.
+int combine_group_msms(hipStream_t s, const g1j *d_c, const g1j *d_pi, bool kilic, const g1j *d_last, const fr *d_sc, uint64_t count, uint64_t R, g1j *d_a, g1j *d_b,
+                       bool to_kilic);
 int combine_group_sums(hipStream_t s, const combine_seed &seed, const g1j *d_c, const g1j *d_pi, bool kilic, const fr *d_x, const fr *d_y, const uint8_t *d_status,
                        uint64_t row0, uint64_t count, uint64_t R, g1j *d_a, g1j *d_b, bool to_kilic) {
-    const uint64_t G = combine_group_count(count, R), stride = combine_term_stride(R), total = G * stride;
-    const msm_plan pb = classic_plan(stride), pa = classic_plan(R);
-    if (!msm_index_range_ok(pb, stride)) return KZG_HIP_ERR_TOO_WIDE;
-    dtmp<g1j> d_pts(s); dtmp<g1a> d_aff(s); dtmp<fr> d_sc(s); dtmp<uint8_t> d_ws(s);
-    CHK(d_pts.alloc(total)); CHK(d_aff.alloc(total)); CHK(d_sc.alloc(total)); CHK(d_ws.alloc(msm_workspace_bytes(pb, stride, G)));
+    const uint64_t stride = combine_term_stride(R), total = combine_group_count(count, R) * stride;
+    if (!msm_index_range_ok(classic_plan(stride), stride)) return KZG_HIP_ERR_TOO_WIDE;
+    dtmp<fr> d_sc(s);
+    CHK(d_sc.alloc(total));
     prof_begin(s, "combine_scalars");
     launch_combine_scalars(s, seed, d_x, d_y, d_status, row0, count, R, d_sc.p);
     prof_end(s, "combine_scalars");
-    launch_combine_points(s, d_c, d_pi, count, R, kilic, d_pts.p);
+    return combine_group_msms(s, d_c, d_pi, kilic, nullptr, d_sc.p, count, R, d_a, d_b, to_kilic);
+}
+// the two MSMs of every group from its term scalars d_sc (combine_term_stride(R) per group): the points of every slice -- d_last (nullable): the
+// point of slot 2 R per group in the form of c and pi, null: the generator -- then B_g over the whole slice and A_g over the proofs
+int combine_group_msms(hipStream_t s, const g1j *d_c, const g1j *d_pi, bool kilic, const g1j *d_last, const fr *d_sc, uint64_t count, uint64_t R, g1j *d_a, g1j *d_b,
+                       bool to_kilic) {
+    const uint64_t G = combine_group_count(count, R), stride = combine_term_stride(R), total = G * stride;
+    const msm_plan pb = classic_plan(stride), pa = classic_plan(R);
+    if (!msm_index_range_ok(pb, stride)) return KZG_HIP_ERR_TOO_WIDE;
+    dtmp<g1j> d_pts(s); dtmp<g1a> d_aff(s); dtmp<uint8_t> d_ws(s);
+    CHK(d_pts.alloc(total)); CHK(d_aff.alloc(total)); CHK(d_ws.alloc(msm_workspace_bytes(pb, stride, G)));
+    launch_combine_points(s, d_c, d_pi, count, R, kilic, d_pts.p, d_last);
     if (kilic) launch_g1_from_kilic(s, d_pts.p, total);
     launch_g1_to_affine(s, d_pts.p, d_aff.p, total);
     prof_begin(s, "combine_msm");
-    launch_msm(s, pb, d_aff.p, d_sc.p, stride, stride, G, d_ws.p, d_b, to_kilic, stride, true);       // B_g: the whole slice
-    launch_msm(s, pa, d_aff.p + R, d_sc.p, stride, R, G, d_ws.p, d_a, to_kilic, stride, true);        // A_g: the proofs with the weights
+    launch_msm(s, pb, d_aff.p, d_sc, stride, stride, G, d_ws.p, d_b, to_kilic, stride, true);       // B_g: the whole slice
+    launch_msm(s, pa, d_aff.p + R, d_sc, stride, R, G, d_ws.p, d_a, to_kilic, stride, true);        // A_g: the proofs with the weights
     prof_end(s, "combine_msm");
     HIPCHK(hipGetLastError());
     return KZG_HIP_OK;
@@ -234,6 +246,71 @@ int combine_group_checks(hipStream_t s, const g2_prepared *gen, const g2_prepare
     CHK(d_p1.alloc(G));
     launch_combine_negate(s, d_a, G, d_p1.p);
     return run_shared_check(s, gen, q1, d_b, d_p1.p, G, h_ok);
+}
+
+// ---- the multi-proof form (verify_combine_multi.hpp, k_verify_combine_multi.hip) ----
+// KZGSettings.CheckProofMulti over `count` host rows of n values, one pairing check per row: IFFT(ys) per row, coefficients times x^-i, x^np,
+// [I(s)]_1 by the batched commitment; then e(C - [I(s)]_1 + [x^np] pi, G2) e(-pi, [s^n]G2) == 1 (kzg_multi_proofs.go:47-75).  The caller
+// holds the handle's mutex, s is the handle's stream, qn the prepared SecretG2[n].
+int multi_checks(kzg_hip_kzg *ks, hipStream_t s, const g2_prepared *gen, const g2_prepared *qn, const void *commitments_g1, const void *proofs_g1, const void *xs_fr,
+                 const void *ys_fr, uint64_t n, uint64_t np, uint64_t count, uint8_t *ok) {
+    dtmp<fr> d_ys(s), d_ip(s), d_x(s), d_xp(s); dtmp<g1j> d_is(s);
+    CHK(d_ys.alloc(count * n)); CHK(d_ip.alloc(count * np)); CHK(d_x.alloc(count)); CHK(d_xp.alloc(count)); CHK(d_is.alloc(count));
+    HIPCHK(hipMemcpyAsync(d_ys.p, ys_fr, count * n * sizeof(fr), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_x.p, xs_fr, count * sizeof(fr), hipMemcpyHostToDevice, s));
+    fr_fft_rows(ks->fs, s, d_ys.p, n, n, d_ip.p, np, count, 1);
+    launch_fr_rows_scale_by_inv_powers(s, d_ip.p, np, d_x.p, count, d_xp.p);
+    CHK(commit_rows(ks, s, d_ip.p, np, count, d_is.p));
+    HIPCHK(hipGetLastError());
+    return kzg_checks(s, gen, qn, commitments_g1, proofs_g1, nullptr, d_is.p, nullptr, d_xp.p, count, ok);
+}
+// From this many rows on kzg_hip_check_proof_multi_batch_combined combines by default: the smallest measured count from which the combined
+// route is faster on all-valid rows at n = 16 AND n = 64 by more than the spread of the repeats (profiles/verify_combine_multi.md; per-row
+// against combined, best .. worst ms).  4 096 rows: 14.4 .. 14.4 against 9.7 .. 9.8 (n = 16), 14.9 .. 15.0 against 10.2 .. 10.4 (n = 64);
+// 65 536: 83.4 against 13.2, 88.6 against 15.7.  Not at 1 024 rows (one group): 8.65 .. 8.71 against 8.74 .. 9.60 and 8.96 .. 8.99 against
+// 9.11 .. 9.31, nor at 64 and 256 rows (7.2 .. 7.6 against 7.8 .. 8.9).
+constexpr uint64_t COMBINE_MULTI_FROM = 4096;
+
+bool combine_multi_route(uint64_t n, uint64_t count) {
+    if (next_pow2(n) > COMBINE_MULTI_NP_MAX) return false;        // a lane of k_combine_multi_poly keeps one coefficient index
+    const knobs::combine_mode m = knobs::verify_combine();
+    return m == knobs::combine_mode::by_count ? count >= COMBINE_MULTI_FROM : m == knobs::combine_mode::always;
+}
+// groups of R rows of n values one chunk of a call holds: the rows' values and coefficients count against COMBINE_CHUNK_BYTES too
+uint64_t combine_multi_chunk_groups(uint64_t R, uint64_t n, uint64_t np) {
+    const uint64_t per = msm_workspace_bytes(classic_plan(combine_term_stride(R)), combine_term_stride(R), 1) + msm_workspace_bytes(classic_plan(np), np, 1) +
+                         R * (n + np) * sizeof(fr);
+    const uint64_t fit = COMBINE_CHUNK_BYTES / per, most = combine_chunk_groups(R);
+    return fit < 1 ? 1 : fit > most ? most : fit;
+}
+// A_g and B_g of the groups of `count` device-resident rows (rows row0 .. of the call): c / pi Kilic images, x Montgomery images, d_coef the
+// inverse transform of the rows' values (np each).  d_j: G x np, receives J_g.  [J_g(s)]_1 is a bucket MSM over the resident affine setup
+// points: no commitment table is built or read.
+int combine_multi_group_sums(kzg_hip_kzg *ks, hipStream_t s, const combine_seed &seed, const g1j *d_c, const g1j *d_pi, const fr *d_x, const fr *d_coef, uint64_t np,
+                             uint64_t row0, uint64_t count, uint64_t R, fr *d_j, g1j *d_a, g1j *d_b, bool to_kilic) {
+    const uint64_t G = combine_group_count(count, R), stride = combine_term_stride(R);
+    const msm_plan pj = classic_plan(np);
+    if (!msm_index_range_ok(classic_plan(stride), stride) || !msm_index_range_ok(pj, np)) return KZG_HIP_ERR_TOO_WIDE;
+    dtmp<fr> d_sc(s), d_part(s); dtmp<g1j> d_js(s); dtmp<uint8_t> d_ws(s);
+    CHK(d_sc.alloc(G * stride)); CHK(d_part.alloc(G * combine_multi_tiles(R) * np)); CHK(d_js.alloc(G)); CHK(d_ws.alloc(msm_workspace_bytes(pj, np, G)));
+    prof_begin(s, "combine_multi_scalars");
+    launch_combine_multi_scalars(s, seed, d_x, d_coef, np, row0, count, R, d_sc.p, d_part.p, d_j);
+    prof_end(s, "combine_multi_scalars");
+    launch_msm(s, pj, ks->d_secret_a, d_j, np, np, G, d_ws.p, d_js.p, true);                           // [J_g(s)]_1 as Kilic images, the form of c and pi
+    HIPCHK(hipGetLastError());
+    return combine_group_msms(s, d_c, d_pi, true, d_js.p, d_sc.p, count, R, d_a, d_b, to_kilic);
+}
+// one chunk of whole groups from host rows: upload, inverse transform, sums.  d_a / d_b: G points, d_j: G x np scalars
+int combine_multi_chunk(kzg_hip_kzg *ks, hipStream_t s, const combine_seed &seed, const g1j *c, const g1j *pi, const fr *xs, const fr *ys, uint64_t n, uint64_t np,
+                        uint64_t row0, uint64_t k, uint64_t R, fr *d_j, g1j *d_a, g1j *d_b, bool to_kilic) {
+    dtmp<g1j> d_c(s), d_pi(s); dtmp<fr> d_x(s), d_ys(s), d_ip(s);
+    CHK(d_c.alloc(k)); CHK(d_pi.alloc(k)); CHK(d_x.alloc(k)); CHK(d_ys.alloc(k * n)); CHK(d_ip.alloc(k * np));
+    HIPCHK(hipMemcpyAsync(d_c.p, c, k * sizeof(g1j), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_pi.p, pi, k * sizeof(g1j), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_x.p, xs, k * sizeof(fr), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_ys.p, ys, k * n * sizeof(fr), hipMemcpyHostToDevice, s));
+    fr_fft_rows(ks->fs, s, d_ys.p, n, n, d_ip.p, np, k, 1);
+    return combine_multi_group_sums(ks, s, seed, d_c.p, d_pi.p, d_x.p, d_ip.p, np, row0, k, R, d_j, d_a, d_b, to_kilic);
 }
 
 }  // namespace
@@ -399,21 +476,59 @@ int kzg_hip_check_proof_multi_batch(kzg_hip_kzg *ks, const void *commitments_g1,
     if (n > fs->W) return KZG_HIP_ERR_TOO_WIDE;                  // "ys is bad, cannot compute FFT" panic, kzg_multi_proofs.go:50-53
     const uint64_t np = next_pow2(n);
     if (np > ks->n_setup) return KZG_HIP_ERR_LEN_MISMATCH;
-    // all rows at once (kzg_hip_check_proof_multi_interpolation's steps over `count` rows): IFFT(ys) per row, coefficients times x^-i, x^np,
-    // [I(s)]_1 by the batched commitment; then e(C - [I(s)]_1 + [x^n] pi, G2) e(-pi, [s^n]G2) == 1   (kzg_multi_proofs.go:47-75)
+    // all rows at once (kzg_hip_check_proof_multi_interpolation's steps over `count` rows, multi_checks)
     dev_guard dg(fs);
     hipStream_t s = fs->stream;
     const g2_prepared *qn = nullptr;
     CHK(g2_pow(g.get(), s, n, &qn));
-    dtmp<fr> d_ys(s), d_ip(s), d_x(s), d_xp(s); dtmp<g1j> d_is(s);
-    CHK(d_ys.alloc(count * n)); CHK(d_ip.alloc(count * np)); CHK(d_x.alloc(count)); CHK(d_xp.alloc(count)); CHK(d_is.alloc(count));
-    HIPCHK(hipMemcpyAsync(d_ys.p, ys_fr, count * n * sizeof(fr), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_x.p, xs_fr, count * sizeof(fr), hipMemcpyHostToDevice, s));
-    fr_fft_rows(fs, s, d_ys.p, n, n, d_ip.p, np, count, 1);
-    launch_fr_rows_scale_by_inv_powers(s, d_ip.p, np, d_x.p, count, d_xp.p);
-    CHK(commit_rows(ks, s, d_ip.p, np, count, d_is.p));
-    HIPCHK(hipGetLastError());
-    return kzg_checks(s, g->d_gen, qn, commitments_g1, proofs_g1, nullptr, d_is.p, nullptr, d_xp.p, count, ok);
+    return multi_checks(ks, s, g->d_gen, qn, commitments_g1, proofs_g1, xs_fr, ys_fr, n, np, count, ok);
+    KZG_CATCH
+}
+
+// CheckProofMulti over `count` rows with one pairing check per group of rows (verify_combine_multi.hpp); the rows of a failing group are
+// re-checked one by one.  The handle's stream under its mutex, as the per-row entry: g2_pow caches the prepared SecretG2[n] on the state.
+int kzg_hip_check_proof_multi_batch_combined(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, uint64_t n,
+                                             uint64_t count, const uint8_t *seed32, uint8_t *ok) {
+    if (!ks) return KZG_HIP_ERR_BAD_ARG;
+    KZG_TRY
+    const std::shared_ptr<g2_state> g = g2_of(ks->g2_mu, ks->g2);
+    if (!g) return KZG_HIP_ERR_BAD_ARG;
+    if (!count) return KZG_HIP_OK;
+    if (!commitments_g1 || !proofs_g1 || !xs_fr || !ys_fr || !ok || n == 0) return KZG_HIP_ERR_BAD_ARG;
+    if (n >= g->h_g2.size()) return KZG_HIP_ERR_LEN_MISMATCH;
+    kzg_hip_fft *fs = ks->fs;
+    if (n > fs->W) return KZG_HIP_ERR_TOO_WIDE;
+    const uint64_t np = next_pow2(n);
+    if (np > ks->n_setup) return KZG_HIP_ERR_LEN_MISMATCH;
+    t_combine = combine_stats{};
+    dev_guard dg(fs);
+    hipStream_t s = fs->stream;
+    const g2_prepared *qn = nullptr;
+    CHK(g2_pow(g.get(), s, n, &qn));
+    if (!combine_multi_route(n, count)) return multi_checks(ks, s, g->d_gen, qn, commitments_g1, proofs_g1, xs_fr, ys_fr, n, np, count, ok);
+    t_combine.route = 1;
+    const combine_seed seed = combine_seed_of(seed32);
+    const uint64_t R = combine_rows(), chunk = combine_multi_chunk_groups(R, n, np) * R;
+    const g1j *c = (const g1j *)commitments_g1, *pi = (const g1j *)proofs_g1; const fr *xs = (const fr *)xs_fr, *ys = (const fr *)ys_fr;
+    std::vector<uint8_t> gok;
+    for (uint64_t i0 = 0; i0 < count; i0 += chunk) {
+        const uint64_t k = count - i0 < chunk ? count - i0 : chunk, G = combine_group_count(k, R);
+        {
+            dtmp<g1j> d_a(s), d_b(s); dtmp<fr> d_j(s);
+            CHK(d_a.alloc(G)); CHK(d_b.alloc(G)); CHK(d_j.alloc(G * np));
+            CHK(combine_multi_chunk(ks, s, seed, c + i0, pi + i0, xs + i0, ys + i0 * n, n, np, i0, k, R, d_j.p, d_a.p, d_b.p, false));
+            gok.assign(G, 0);
+            CHK(combine_group_checks(s, g->d_gen, qn, d_a.p, d_b.p, G, gok.data()));
+        }
+        t_combine.groups += G;
+        for (uint64_t gi = 0; gi < G; gi++) {
+            const uint64_t b = i0 + combine_group_begin(gi, R), e = i0 + combine_group_end(gi, R, k);
+            if (gok[gi]) { memset(ok + b, 1, e - b); continue; }
+            t_combine.failed++; t_combine.rechecked += e - b;
+            CHK(multi_checks(ks, s, g->d_gen, qn, c + b, pi + b, xs + b, ys + b * n, n, np, e - b, ok + b));
+        }
+    }
+    return KZG_HIP_OK;
     KZG_CATCH
 }
 
@@ -554,6 +669,37 @@ int kzg_hip_test_combine_points(kzg_hip_kzg *ks, const void *commitments_g1, con
     HIPCHK(hipStreamSynchronize(s));
     return KZG_HIP_OK;
     KZG_CATCH
+}
+// the multi-proof form: A_g and B_g likewise, and J_g as G x np Montgomery values
+int kzg_hip_test_combine_multi_points(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, uint64_t n, uint64_t count,
+                                      const uint8_t *seed32, void *out_a_g1, void *out_b_g1, void *out_j_fr) {
+    if (!ks || !seed32 || n == 0 || (count && (!commitments_g1 || !proofs_g1 || !xs_fr || !ys_fr || !out_a_g1 || !out_b_g1 || !out_j_fr))) return KZG_HIP_ERR_BAD_ARG;
+    if (!count) return KZG_HIP_OK;
+    KZG_TRY
+    kzg_hip_fft *fs = ks->fs;
+    const uint64_t np = next_pow2(n);
+    if (n > fs->W || np > COMBINE_MULTI_NP_MAX) return KZG_HIP_ERR_TOO_WIDE;
+    if (np > ks->n_setup) return KZG_HIP_ERR_LEN_MISMATCH;
+    const combine_seed seed = combine_seed_of(seed32);
+    const uint64_t R = combine_rows(), G = combine_group_count(count, R);
+    if (G > combine_multi_chunk_groups(R, n, np)) return KZG_HIP_ERR_TOO_WIDE;
+    dev_guard dg(fs);
+    hipStream_t s = fs->stream;
+    dtmp<g1j> d_a(s), d_b(s); dtmp<fr> d_j(s);
+    CHK(d_a.alloc(G)); CHK(d_b.alloc(G)); CHK(d_j.alloc(G * np));
+    CHK(combine_multi_chunk(ks, s, seed, (const g1j *)commitments_g1, (const g1j *)proofs_g1, (const fr *)xs_fr, (const fr *)ys_fr, n, np, 0, count, R, d_j.p, d_a.p, d_b.p,
+                            true));
+    HIPCHK(hipMemcpyAsync(out_a_g1, d_a.p, G * sizeof(g1j), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_b_g1, d_b.p, G * sizeof(g1j), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_j_fr, d_j.p, G * np * sizeof(fr), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return KZG_HIP_OK;
+    KZG_CATCH
+}
+int kzg_hip_test_combine_multi_route(uint64_t n, uint64_t count, uint64_t out[2]) {
+    if (!out || n == 0) return KZG_HIP_ERR_BAD_ARG;
+    out[0] = combine_multi_route(n, count) ? 1 : 0; out[1] = COMBINE_MULTI_FROM;
+    return KZG_HIP_OK;
 }
 int kzg_hip_test_combine_stats(uint64_t out[6]) {
     if (!out) return KZG_HIP_ERR_BAD_ARG;

@@ -247,12 +247,19 @@ void launch_eth_tx_hashes_check(hipStream_t s, const uint8_t *c48, const uint8_t
 struct combine_seed;
 // term scalars (Montgomery) of rows row0 .. row0 + count of the call from their x and y (Montgomery); status (nullable): non-zero rows get weight 0
 void launch_combine_scalars(hipStream_t s, const combine_seed &seed, const fr *xs, const fr *ys, const uint8_t *status, uint64_t row0, uint64_t count, uint64_t R, fr *sc);
-// term points as they came in (Kilic images when kilic, else device-internal), the generator in the same form
-void launch_combine_points(hipStream_t s, const g1j *c, const g1j *pi, uint64_t count, uint64_t R, bool kilic, g1j *out);
+// term points as they came in (Kilic images when kilic, else device-internal); slot 2 R of group g: the generator in the same form, or last[g]
+void launch_combine_points(hipStream_t s, const g1j *c, const g1j *pi, uint64_t count, uint64_t R, bool kilic, g1j *out, const g1j *last = nullptr);
 void launch_combine_negate(hipStream_t s, const g1j *a, uint64_t n, g1j *out);   // out[g] = -a[g]
 // eth form: z, y as Montgomery images and status 0 / 2 / 3 per row from the bytes and the decompression flags of commitment and proof
 void launch_eth_combine_fields(hipStream_t s, const uint8_t *zs, const uint8_t *ys, const uint8_t *c_bad, const uint8_t *pi_bad, uint64_t n, fr *z_out, fr *y_out,
                                uint8_t *status);
+
+// ---------------- k_verify_combine_multi.hip ----------------
+// the multi-proof form (verify_combine_multi.hpp) over rows row0 .. row0 + count of the call: coef = the inverse transform of the rows' values,
+// np <= COMBINE_MULTI_NP_MAX coefficients per row.  sc: the groups' slices (r at j, r x^np at R + j, -1 at 2 R); partials: groups x
+// combine_multi_tiles(R) x np scratch; J: groups x np, the scalars of [J_g(s)]_1 over the setup's first np points
+void launch_combine_multi_scalars(hipStream_t s, const combine_seed &seed, const fr *xs, const fr *coef, uint64_t np, uint64_t row0, uint64_t count, uint64_t R, fr *sc,
+                                  fr *partials, fr *J);
 
 // profiling hook (HIP events around the dominant kernel), see capi.hip
 void prof_begin(hipStream_t s, const char *name);

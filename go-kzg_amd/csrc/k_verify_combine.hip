@@ -42,23 +42,27 @@ void launch_combine_scalars(hipStream_t s, const combine_seed &seed, const fr *x
 }
 
 // The term points of every group in the layout of the scalars, as they came in (Kilic images when `kilic`, else device-internal ones): one lane
-// per slot.  Slots of rows beyond the count get the point at infinity (their scalar is 0), the last slot of a slice the generator.
-__global__ __launch_bounds__(COMBINE_BLOCK) void k_combine_points(const g1j *c, const g1j *pi, uint64_t count, uint64_t R, int kilic, uint64_t total, g1j *out) {
+// per slot.  Slots of rows beyond the count get the point at infinity (their scalar is 0), the last slot of a slice the generator, or the group's
+// own point last[g] (in the form of c and pi) when last is not null.
+__global__ __launch_bounds__(COMBINE_BLOCK) void k_combine_points(const g1j *c, const g1j *pi, const g1j *last, uint64_t count, uint64_t R, int kilic, uint64_t total,
+                                                                  g1j *out) {
     const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (t >= total) return;
     const uint64_t stride = combine_term_stride(R), g = t / stride, j = t % stride;
     g1j p = g1_inf();
-    if (j == 2 * R) p = g1_generator_internal();
-    else {
+    if (j == 2 * R) {
+        if (last) { out[t] = last[g]; return; }
+        p = g1_generator_internal();
+    } else {
         const uint64_t row = combine_group_begin(g, R) + (j < R ? j : j - R);
         if (row < count) { out[t] = j < R ? c[row] : pi[row]; return; }
     }
     out[t] = kilic ? g1_to_kilic(p) : p;
 }
-void launch_combine_points(hipStream_t s, const g1j *c, const g1j *pi, uint64_t count, uint64_t R, bool kilic, g1j *out) {
+void launch_combine_points(hipStream_t s, const g1j *c, const g1j *pi, uint64_t count, uint64_t R, bool kilic, g1j *out, const g1j *last) {
     if (!count) return;
     const uint64_t total = combine_group_count(count, R) * combine_term_stride(R);
-    hipLaunchKernelGGL(k_combine_points, dim3((uint32_t)((total + COMBINE_BLOCK - 1) / COMBINE_BLOCK)), dim3(COMBINE_BLOCK), 0, s, c, pi, count, R, kilic ? 1 : 0, total, out);
+    hipLaunchKernelGGL(k_combine_points, dim3((uint32_t)((total + COMBINE_BLOCK - 1) / COMBINE_BLOCK)), dim3(COMBINE_BLOCK), 0, s, c, pi, last, count, R, kilic ? 1 : 0, total, out);
 }
 
 // p1[g] = -A_g: the second G1 input of the group check e(B_g, [1]G2) e(-A_g, [s]G2) == 1

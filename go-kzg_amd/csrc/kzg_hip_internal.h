@@ -78,6 +78,15 @@ int kzg_hip_test_pairing_route(uint64_t n, uint64_t out[2]);
 int kzg_hip_test_combine_points(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, uint64_t count,
                                 const uint8_t *seed32, void *out_a_g1, void *out_b_g1);
 int kzg_hip_test_combine_stats(uint64_t out[6]);
+/* the same for kzg_hip_check_proof_multi_batch_combined (verify_combine_multi.hpp).
+ * kzg_hip_test_combine_multi_points: A_g and B_g = sum r_i C_i + sum (r_i x_i^np) pi_i - [J_g(s)]_1 of every group as normalised Kilic images, and
+ * J_g[j] = sum r_i x_i^-j c_i[j] as ceil(count / rows) x np Montgomery values.  KZG_HIP_ERR_TOO_WIDE for more groups than one chunk holds and
+ * for np > 256.
+ * kzg_hip_test_combine_multi_route: out[0] = 1 when a call with `count` rows of n values would combine under the current environment, 0 the
+ * per-row path; out[1] = the count from which the default combines */
+int kzg_hip_test_combine_multi_points(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, uint64_t n, uint64_t count,
+                                      const uint8_t *seed32, void *out_a_g1, void *out_b_g1, void *out_j_fr);
+int kzg_hip_test_combine_multi_route(uint64_t n, uint64_t count, uint64_t out[2]);
 
 /* test hook of the G2 half of a setup (capi_verify.hip): how many times the handle built its fixed-base table of bls.GenG2 -- 0 before the first
  * kzg_hip_g2_mul_generator_vec / kzg_hip_generate_testing_setup_g2, 1 ever after, however many threads made the first call at once */

@@ -105,3 +105,33 @@ func (ks *KZGSettings) CheckProofMultiBatch(commitments, proofs []bls.G1Point, x
 		C.uint64_t(n), (*C.uint8_t)(unsafe.Pointer(&ok[0]))))
 	return okMask(ok)
 }
+
+// CheckProofMultiBatchCombined: the mask of CheckProofMultiBatch with one pairing check per group of rows (the check a DAS sampler makes on
+// the proofs of DAUsingFK20Multi; the rows of a failing group are re-checked one by one).  seed as CheckProofSingleBatchCombined: nil draws
+// it from the operating system, a seed the prover can know in advance voids the 2^-128 bound.  Presupposes points of G1, as CheckProofMulti does.
+func (ks *KZGSettings) CheckProofMultiBatchCombined(commitments, proofs []bls.G1Point, xs []bls.Fr, ys [][]bls.Fr, seed *[32]byte) []bool {
+	defer runtime.KeepAlive(ks)
+	n := len(commitments)
+	if len(proofs) != n || len(xs) != n || len(ys) != n {
+		panic("CheckProofMultiBatchCombined: slices of different lengths")
+	}
+	if n == 0 {
+		return nil
+	}
+	m := len(ys[0])
+	flat := make([]bls.Fr, 0, n*m)
+	for _, row := range ys {
+		if len(row) != m {
+			panic("CheckProofMultiBatchCombined: ys rows of different lengths")
+		}
+		flat = append(flat, row...)
+	}
+	var sp *C.uint8_t
+	if seed != nil {
+		sp = (*C.uint8_t)(unsafe.Pointer(&seed[0]))
+	}
+	ok := make([]uint8, n)
+	hipMust(C.kzg_hip_check_proof_multi_batch_combined(ks.hipSecretG2(), g1Ptr(commitments), g1Ptr(proofs), frPtr(xs), frPtr(flat), C.uint64_t(m),
+		C.uint64_t(n), sp, (*C.uint8_t)(unsafe.Pointer(&ok[0]))))
+	return okMask(ok)
+}

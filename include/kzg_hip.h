@@ -300,6 +300,16 @@ int kzg_hip_check_proof_single_batch_combined(kzg_hip_kzg *ks, const void *commi
                                               uint64_t count, const uint8_t *seed32, uint8_t *ok);
 int kzg_hip_eth_verify_kzg_proof_batch_combined(kzg_hip_eth *eth, const void *commitments48, const void *zs_le32, const void *ys_le32, const void *proofs48,
                                                 uint64_t count, const uint8_t *seed32, uint8_t *result);
+/* kzg_hip_check_proof_multi_batch likewise (the check a DAS sampler makes on coset proofs): arguments, error codes and output bytes are the
+ * per-row entry's, the weights, the seed, the groups and the two switches those of the single form above.  With c_i the inverse transform of
+ * the zero-padded ys_i and np = next_pow2(n), per group
+ *   A_g = sum r_i pi_i,   J_g[j] = sum r_i x_i^-j c_i[j] (j < np),   B_g = sum r_i C_i + sum (r_i x_i^np) pi_i - [J_g(s)]_1,
+ * and the group passes when e(B_g, [1]G2) e(-A_g, [s^n]G2) == 1: one pairing check, two multi-scalar multiplications over the group's points
+ * and one of np terms over the setup per group, where the per-row entry commits to every row's np coefficients.  The combination builds and
+ * reads no commitment table.  x_i == 0 follows the reference (InvModFr(0) == 0).  Rows of more than 256 values (np > 256) always take the
+ * per-row path.  PRESUPPOSES POINTS OF G1, as CheckProofMulti does; the bound 2^-128 and the warning about known seeds hold as above. */
+int kzg_hip_check_proof_multi_batch_combined(kzg_hip_kzg *ks, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, uint64_t n,
+                                             uint64_t count, const uint8_t *seed32, uint8_t *ok);
 /* eth.VerifyAggregateKZGProof (eth/eth.go:155-172) over `sidecars` blocks.  blob_counts[j] blobs belong to block j (0 is valid); blobs_le32 holds
  * all blobs in block order (sum(blob_counts) x n x 32 little-endian bytes), commitments48 the expected commitments in the same order, proofs48 one
  * aggregated proof per block.  result[j]: 1 valid, 0 the pairing check failed, 2 a field element of one of the block's blobs is >= r ("could not

@@ -227,6 +227,15 @@ class KZGSettings {
         detail::must(kzg_hip_check_proof_multi_batch(h_, commitments.data(), proofs.data(), xs.data(), ys.data(), n, ok.size(), ok.data()));
         return std::vector<bool>(ok.begin(), ok.end());
     }
+    // the same mask with one pairing check per group of rows (kzg_hip_check_proof_multi_batch_combined); seed32: null draws the weights' seed
+    // from the operating system, 32 bytes make a run reproducible (a seed the prover can know in advance voids the 2^-128 bound)
+    std::vector<bool> CheckProofMultiBatchCombined(const std::vector<G1Point> &commitments, const std::vector<G1Point> &proofs, const std::vector<Fr> &xs,
+                                                   const std::vector<Fr> &ys, uint64_t n, const uint8_t *seed32 = nullptr) const {
+        std::vector<uint8_t> ok(commitments.size());
+        if (proofs.size() != ok.size() || xs.size() != ok.size() || ys.size() != ok.size() * n) throw Panic(KZG_HIP_ERR_LEN_MISMATCH, "slice lengths");
+        detail::must(kzg_hip_check_proof_multi_batch_combined(h_, commitments.data(), proofs.data(), xs.data(), ys.data(), n, ok.size(), seed32, ok.data()));
+        return std::vector<bool>(ok.begin(), ok.end());
+    }
 
   private:
     kzg_hip_kzg *h_ = nullptr;
