@@ -83,7 +83,11 @@ struct kzg_hip_kzg {
     g1a *d_secret_a = nullptr;   // affine table for the MSM
     g1a *d_fixed = nullptr;      // fixed-base window table (lazily built)
     msm_plan fixed_plan{};
+    g1a *d_shared = nullptr;     // shared-window table d P_i for large batches (ensure_shared_table); built and freed under tab_mu (unique) and the handle mutex
+    msm_plan shared_plan{};      // c, nwin = ceil(128 / c) windows per GLV half, nb = 2^(c-1); c == 0xffffffff: none is worth its memory at this budget
+    bool shared_first = false;   // the shared table was sized from the WHOLE budget (it replaced the all-window table, or came first): the all-window table gets the remainder
     double budget_gb = -1.0;             // fixed-base table budget; < 0: default policy (ensure_fixed_table)
+    double resolved_budget_gb = -1.0;    // what the default policy gave when the first resident table was sized (fb_handle_budget_gb)
     std::atomic<bool> projective{false}; // kzg_hip_kzg_set_projective_outputs: table-walk results leave as Jacobian images with Z != 1 (no inversion per result)
     hipStream_t copy_stream = nullptr;   // uploads of the host-buffer batch entry point, overlapped with the walk of the previous chunk
     hipEvent_t copy_done[2] = {nullptr, nullptr};
@@ -271,7 +275,8 @@ int kzg_settings_build(kzg_hip_fft *fs, const void *points_g1, uint64_t n, kzg_h
 int ensure_fixed_table(kzg_hip_kzg *ks, hipStream_t);   // capi_kzg.hip
 const void *host_mapped_pointer(const void *host, size_t bytes);
 int h2d_copy(void *dst, const void *src, size_t bytes, hipStream_t s);   // capi_kzg.hip: cut at the boundaries of registered ranges   // capi_kzg.hip
-int commit_rows(kzg_hip_kzg *ks, hipStream_t s, const fr *d_sc, uint64_t n, uint64_t batch, g1j *d_out, uint64_t sc_stride = 0, bool to_kilic = true);   // capi_kzg.hip
+int commit_rows(kzg_hip_kzg *ks, hipStream_t s, const fr *d_sc, uint64_t n, uint64_t batch, g1j *d_out, uint64_t sc_stride = 0, bool to_kilic = true, bool may_share = false);   // capi_kzg.hip (may_share: the caller went through prepare_shared_table and holds the handle mutex)
+int prepare_shared_table(kzg_hip_kzg *ks, uint64_t batch);   // capi_kzg.hip: before the handle mutex is taken
 double table_budget_gb(knobs::opt_gb env, double cap_gb, double headroom_gb);   // capi_kzg.hip
 int lincomb_points_rows(kzg_hip_points *pts, hipStream_t s, const fr *d_sc, uint64_t n, uint64_t batch, g1j *d_out, uint64_t sc_stride = 0, bool holds_mu = false);   // capi_core.hip
 int lincomb_points_coalesced(kzg_hip_points *pts, const void *scalars_fr, uint64_t n, void *out_g1);   // capi_kzg.hip

@@ -37,7 +37,7 @@ void kzg_hip_kzg_settings_free(kzg_hip_kzg *ks) {
     if (!ks) return;
     hipSetDevice(ks->fs->device);
     hipDeviceSynchronize();   // _dev callers may still have work in flight that reads the tables: drain the device first
-    hipFree(ks->d_secret); hipFree(ks->d_secret_a); hipFree(ks->d_fixed);
+    hipFree(ks->d_secret); hipFree(ks->d_secret_a); hipFree(ks->d_fixed); hipFree(ks->d_shared);
     if (ks->copy_stream) { stream_cache_disown(ks->copy_stream); hipStreamDestroy(ks->copy_stream); }
     for (int i = 0; i < 2; i++) if (ks->copy_done[i]) hipEventDestroy(ks->copy_done[i]);
     (void)hipGetLastError();
@@ -76,18 +76,28 @@ uint32_t fb_windows(uint32_t c) {
 #endif
 // windows of the GLV walk: both halves of a split scalar are below 2^126.5 (glv_split_signed), so the top signed digit cannot carry out as soon as
 // c * nwin >= 128
-uint32_t fb_windows_glv(uint32_t c) { return (128 + c - 1) / c; }
+uint32_t fb_windows_glv(uint32_t c) { return fb_shared_windows(c); }
 bool fb_glv_enabled() { return knobs::fb_glv(); }
+static double fb_plan_bytes(const msm_plan &p) { return (double)p.nwin * (double)p.table_n * (double)p.nb * sizeof(g1a); }
+// the handle's ONE budget: the default policy depends on the free HBM of the moment, so it is resolved when the handle's first table is sized and kept while
+// a table is resident -- the second table is paid from the same figure whatever has been allocated on the device since
+static double fb_handle_budget_gb(kzg_hip_kzg *ks) {
+    if (ks->budget_gb >= 0.0) return ks->budget_gb;
+    if (!((ks->d_fixed || ks->d_shared) && ks->resolved_budget_gb >= 0.0)) ks->resolved_budget_gb = table_budget_gb(knobs::fb_budget_gb(), FB_DEFAULT_BUDGET_GB, 24.0);
+    return ks->resolved_budget_gb;
+}
+// window sizes that are dominated by a smaller table with the same number of additions per point are skipped: GLV c = 14 (2 x 10 windows, 32 GB)
+// against c = 13 (2 x 10, 16 GB); plain c = 15 (18 windows, 116 GB) measured slower than c = 14 (19 windows, 61 GB)
+static bool fb_window_size_skipped(uint32_t c, bool glv) { return glv ? (c == 14) : (c == 15); }
+// A resident shared-window table (below) is paid from the same budget: the all-window table gets what it leaves.
 int ensure_fixed_table(kzg_hip_kzg *ks, hipStream_t) {
     if (ks->d_fixed || ks->fixed_plan.c == 0xffffffffu) return KZG_HIP_OK;
     hipStream_t s = ks->fs->stream;
-    double budget_gb = ks->budget_gb >= 0.0 ? ks->budget_gb : table_budget_gb(knobs::fb_budget_gb(), FB_DEFAULT_BUDGET_GB, 24.0);
+    const double budget_gb = fb_handle_budget_gb(ks) - (ks->d_shared ? (double)ks->shared_plan.table_n * (double)ks->shared_plan.nb * sizeof(g1a) / 1e9 : 0.0);
     if (ks->n_setup < 64) { ks->fixed_plan.c = 0xffffffffu; return KZG_HIP_OK; }   // classic path only
     const bool glv = fb_glv_enabled();
     for (uint32_t c = 16; c >= 5; c--) {
-        // window sizes that are dominated by a smaller table with the same number of additions per point are skipped: GLV c = 14 (2 x 10 windows, 32 GB)
-        // against c = 13 (2 x 10, 16 GB); plain c = 15 (18 windows, 116 GB) measured slower than c = 14 (19 windows, 61 GB)
-        if (glv ? (c == 14) : (c == 15)) continue;
+        if (fb_window_size_skipped(c, glv)) continue;
         const uint32_t nwin = glv ? fb_windows_glv(c) : fb_windows(c);
         double bytes = (double)nwin * (double)ks->n_setup * (double)(1u << (c - 1)) * sizeof(g1a);
         if (bytes > budget_gb * 1e9) continue;
@@ -106,13 +116,124 @@ int ensure_fixed_table(kzg_hip_kzg *ks, hipStream_t) {
     return KZG_HIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The shared-window table for LARGE batches: T_s[i D + d - 1] = d SecretG1[i], one accumulator per window and a Horner finish (k_msm.hip).  Without the
+// window dimension the budget buys wider digits: 103 GB are signed 19-bit digits, 7 windows per GLV half, 14 additions per coefficient against the 16 of the
+// all-window table of that size; 51 / 13 / 6.4 / 3.2 GB give 16 / 16 / 18 / 20 against 18 / 20 / 22 / 24.  The finish is ~0.6 ms of latency per launch, so
+// only batches of at least FB_SHARED_MIN_BATCH rows take it (kzg_hip_commit_to_poly_batch and _dev; eth settings, cached point sets, proofs and the coalesced
+// one-polynomial calls stay on the all-window table).  Both tables are built on demand from the handle's ONE budget:
+//   * a small call builds the all-window table by the rule above from the budget less a resident shared table, and never evicts one;
+//   * a large call builds the shared table from the budget less the all-window table if that gives fewer additions than the all-window table offers;
+//     otherwise, if the WHOLE budget gives fewer, the all-window table is freed and the shared table takes the whole budget (110 GB: the 103 GB all-window
+//     table leaves room for 18 additions, so it is replaced by 14).  Later small calls get the all-window table the remainder affords (c = 11, 24 additions);
+//     on such a handle batches from FB_SHARED_MIN_BATCH_REPLACED rows take the shared walk.  KZG_HIP_FB_LAYOUT=windows turns all of this off.
+// c is the largest of 19 .. 5 that fits, less those with as many windows as a smaller c (18, 17 -> 16; 14 -> 13).  Allocation failures fall to the next c.
+// ---------------------------------------------------------------------------------------------------------
+#ifndef FB_SHARED_MIN_BATCH
+#define FB_SHARED_MIN_BATCH 2048            // measured crossover against the c = 16 all-window walk: 1024 rows 10.28 vs 10.64 ms (within the spread), 2048 rows 19.3 vs 21.1 ms (profiles/shared_window_walk.md)
+#endif
+#ifndef FB_SHARED_CHUNK
+#define FB_SHARED_CHUNK 4096                // rows per launch of the shared walk (bounds its digit workspace; one launch for the headline batch)
+#endif
+#ifndef FB_SHARED_MIN_BATCH_REPLACED
+#define FB_SHARED_MIN_BATCH_REPLACED 256    // ... against the c = 11 walk that a handle keeps beside a shared table of the whole default budget: 128 rows 2.03 vs 2.04 ms, 256 rows 3.12 vs 3.94 ms
+#endif
+static uint32_t fb_shared_pick(uint64_t n_setup, double bytes, uint32_t below = 20) {
+    for (uint32_t c = below - 1; c >= 5; c--) {
+        if (c > 5 && fb_shared_windows(c - 1) == fb_shared_windows(c)) continue;
+        if ((double)n_setup * (double)(1u << (c - 1)) * sizeof(g1a) <= bytes) return c;
+    }
+    return 0;
+}
+static uint32_t fb_plan_additions(const msm_plan &p) { return p.glv ? 2 * p.nwin : p.nwin; }
+// additions per coefficient of the all-window table that ensure_fixed_table would build from `bytes`; UINT32_MAX: none fits
+static uint32_t fb_windows_additions_at(uint64_t n_setup, double bytes, bool glv) {
+    for (uint32_t c = 16; c >= 5; c--) {
+        if (fb_window_size_skipped(c, glv)) continue;
+        const uint32_t nwin = glv ? fb_windows_glv(c) : fb_windows(c);
+        if ((double)nwin * (double)n_setup * (double)(1u << (c - 1)) * sizeof(g1a) <= bytes) return glv ? 2 * nwin : nwin;
+    }
+    return UINT32_MAX;
+}
+// rows from which a batch walks the shared table of this handle
+static uint64_t fb_shared_threshold(const kzg_hip_kzg *ks) {
+    if (const uint64_t forced = knobs::fb_shared_min_batch()) return forced;
+    if (knobs::fb_layout() == knobs::fb_layout_mode::shared) return 1;
+    return ks->shared_first ? FB_SHARED_MIN_BATCH_REPLACED : FB_SHARED_MIN_BATCH;
+}
+// builds the largest shared table below 2 * `fewer_than` additions that fits `bytes`; false: none
+static bool fb_shared_build(kzg_hip_kzg *ks, double bytes, uint32_t fewer_than) {
+    hipStream_t s = ks->fs->stream;
+    for (uint32_t c = fb_shared_pick(ks->n_setup, bytes); c && 2 * fb_shared_windows(c) < fewer_than; c = fb_shared_pick(ks->n_setup, bytes, c)) {
+        msm_plan p{};
+        p.c = c; p.nwin = fb_shared_windows(c); p.nb = 1u << (c - 1); p.ngroups = 1; p.fixed = 1; p.glv = 1; p.table_n = ks->n_setup;
+        g1a *tab = nullptr;
+        if (hipMalloc((void **)&tab, (size_t)ks->n_setup * p.nb * sizeof(g1a)) != hipSuccess) { (void)hipGetLastError(); continue; }   // retry smaller
+        hipError_t e = launch_fb_build_shared(s, ks->d_secret_a, ks->n_setup, c, tab);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hipGetLastError(); hipFree(tab); continue; }
+        ks->d_shared = tab; ks->shared_plan = p;
+        return true;
+    }
+    return false;
+}
+// callers hold tab_mu (unique) and the handle mutex
+static int ensure_shared_table(kzg_hip_kzg *ks) {
+    if (ks->d_shared || ks->shared_plan.c == 0xffffffffu) return KZG_HIP_OK;
+    if (ks->n_setup < 64 || !fb_glv_enabled()) { ks->shared_plan.c = 0xffffffffu; return KZG_HIP_OK; }
+    const double budget = fb_handle_budget_gb(ks) * 1e9;
+    if (ks->d_fixed) {
+        if (fb_shared_build(ks, budget - fb_plan_bytes(ks->fixed_plan), fb_plan_additions(ks->fixed_plan))) return KZG_HIP_OK;   // both tables resident
+        const uint32_t c = fb_shared_pick(ks->n_setup, budget);
+        if (!c || 2 * fb_shared_windows(c) >= fb_plan_additions(ks->fixed_plan)) { ks->shared_plan.c = 0xffffffffu; return KZG_HIP_OK; }
+        HIPCHK(hipDeviceSynchronize());                      // walks of the all-window table in flight (as kzg_hip_kzg_set_table_budget_gb)
+        HIPCHK(hipFree(ks->d_fixed));
+        ks->d_fixed = nullptr; ks->fixed_plan = msm_plan{};
+    }
+    // the whole budget: worth it if it beats what the all-window rule would build from the same bytes
+    if (fb_shared_build(ks, budget, fb_windows_additions_at(ks->n_setup, budget, true))) ks->shared_first = true;
+    else ks->shared_plan.c = 0xffffffffu;
+    return KZG_HIP_OK;
+}
+// The batch entry points call this BEFORE they take the handle mutex: replacing the all-window table excludes the coalesced batches that walk it under
+// tab_mu (shared), and tab_mu is always taken before the handle mutex.
+int prepare_shared_table(kzg_hip_kzg *ks, uint64_t batch) {
+    if (knobs::fb_layout() == knobs::fb_layout_mode::windows) return KZG_HIP_OK;
+    {
+        dev_guard g(ks->fs);
+        if (ks->d_shared || ks->shared_plan.c == 0xffffffffu || batch < fb_shared_threshold(ks)) return KZG_HIP_OK;
+    }
+    std::unique_lock<std::shared_mutex> tl(ks->tab_mu);
+    dev_guard g(ks->fs);
+    return ensure_shared_table(ks);
+}
+
 // MSM of `batch` resident scalar rows against SecretG1[:n]; out = batch normalised points (device).  The partial-sum / bucket
 // workspace is allocated per call, stream-ordered on the launch stream (hipMallocAsync pool: no device synchronisation after the
 // first use), so concurrent callers on different streams never share scratch memory.
-int commit_rows(kzg_hip_kzg *ks, hipStream_t s, const fr *d_sc, uint64_t n, uint64_t batch, g1j *d_out, uint64_t sc_stride, bool to_kilic) {
-    CHK(ensure_fixed_table(ks, s));
-    bool fixed = ks->d_fixed != nullptr;
+int commit_rows(kzg_hip_kzg *ks, hipStream_t s, const fr *d_sc, uint64_t n, uint64_t batch, g1j *d_out, uint64_t sc_stride, bool to_kilic, bool may_share) {
     if (!sc_stride) sc_stride = n;
+    bool share = may_share && ks->d_shared && knobs::fb_layout() != knobs::fb_layout_mode::windows && batch >= fb_shared_threshold(ks);
+    if (!share) {
+        CHK(ensure_fixed_table(ks, s));
+        share = may_share && !ks->d_fixed && ks->d_shared && knobs::fb_layout() != knobs::fb_layout_mode::windows;   // the remainder of the budget holds no all-window table
+    }
+    if (share) {
+        // the digit words are 2 W n x 4 bytes per row (0.94 GB for 4096 blobs at W = 7): batches beyond FB_SHARED_CHUNK rows walk in pieces that reuse one
+        // workspace in stream order, and if even that cannot be had the batch takes the all-window (or bucket) path below -- a commitment never fails for lack of HBM
+        const uint64_t piece = batch < FB_SHARED_CHUNK ? batch : FB_SHARED_CHUNK;
+        dtmp<uint8_t> d_ws(s);
+        if (d_ws.alloc(fb_shared_workspace_bytes(n, piece, ks->shared_plan.c)) == KZG_HIP_OK) {
+            const bool projective = to_kilic && ks->projective.load(std::memory_order_relaxed);
+            for (uint64_t b0 = 0; b0 < batch; b0 += piece)
+                launch_fb_msm_shared(s, ks->d_shared, ks->shared_plan.c, d_sc + b0 * sc_stride, sc_stride, n, batch - b0 < piece ? batch - b0 : piece, d_ws.p, d_out + b0, to_kilic, projective);
+            HIPCHK(hipGetLastError());
+            return KZG_HIP_OK;
+        }
+        (void)hipGetLastError();
+        CHK(ensure_fixed_table(ks, s));
+    }
+    bool fixed = ks->d_fixed != nullptr;
     msm_plan p = fixed ? ks->fixed_plan : classic_plan(ks->n_setup);
     if (!fixed && !msm_index_range_ok(p, n)) return KZG_HIP_ERR_TOO_WIDE;
     size_t ws_main = fixed ? fb_partials_bytes(n, batch) : msm_workspace_bytes(p, n, batch);
@@ -128,8 +249,10 @@ int kzg_hip_kzg_set_table_budget_gb(kzg_hip_kzg *ks, double gb) {
     if (!ks || !(gb >= 0.0)) return KZG_HIP_ERR_BAD_ARG;
     std::unique_lock<std::shared_mutex> tl(ks->tab_mu);        // waits for coalesced batches that are walking the current table
     dev_guard g(ks->fs);
-    if (ks->d_fixed) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(ks->d_fixed)); ks->d_fixed = nullptr; }
-    ks->fixed_plan = msm_plan{};
+    if (ks->d_fixed || ks->d_shared) HIPCHK(hipDeviceSynchronize());
+    if (ks->d_fixed) { HIPCHK(hipFree(ks->d_fixed)); ks->d_fixed = nullptr; }
+    if (ks->d_shared) { HIPCHK(hipFree(ks->d_shared)); ks->d_shared = nullptr; }
+    ks->fixed_plan = msm_plan{}; ks->shared_plan = msm_plan{}; ks->shared_first = false; ks->resolved_budget_gb = -1.0;
     ks->budget_gb = gb;
     return KZG_HIP_OK;
 }
@@ -139,8 +262,9 @@ int kzg_hip_commit_to_poly_batch_dev(kzg_hip_kzg *ks, const void *d_coeffs_fr, u
     if (n > ks->n_setup) return KZG_HIP_ERR_LEN_MISMATCH;   // slice bounds of SecretG1[:len(coeffs)], kzg_single_proofs.go:18
     if (!batch) return KZG_HIP_OK;
     if (n == 0 || !d_coeffs_fr) return KZG_HIP_ERR_BAD_ARG;
+    CHK(prepare_shared_table(ks, batch));
     dev_guard g(ks->fs);
-    return commit_rows(ks, (hipStream_t)stream, (const fr *)d_coeffs_fr, n, batch, (g1j *)d_out_g1);
+    return commit_rows(ks, (hipStream_t)stream, (const fr *)d_coeffs_fr, n, batch, (g1j *)d_out_g1, 0, true, true);
 }
 // Ranges pinned through kzg_hip_host_register: the in-place paths need the EXTENT of a pinned range, which hipPointerGetAttributes does not report.
 namespace {
@@ -233,29 +357,33 @@ int kzg_hip_commit_to_poly_batch(kzg_hip_kzg *ks, const void *coeffs_fr, uint64_
     if (!batch) return KZG_HIP_OK;
     if (n == 0) { for (uint64_t b = 0; b < batch; b++) set_inf_image((uint8_t *)out_g1 + b * sizeof(g1j)); return KZG_HIP_OK; }
     if (!coeffs_fr) return KZG_HIP_ERR_BAD_ARG;
+    // Large batches are uploaded in chunks on a second stream: the copy of chunk i + 1 (from pageable host memory it occupies the
+    // calling thread) runs while the GPU walks chunk i.  Chunks keep >= 256 blobs so that a walk still fills one round of waves.
+    uint64_t chunk = batch >= 1024 ? 512 : (batch >= 512 ? 256 : batch);
+    if (n * sizeof(fr) < (64u << 10)) chunk = batch;
+    const fr *mapped = nullptr;
+    { dev_select sel(ks->fs); mapped = (const fr *)host_mapped_pointer(coeffs_fr, (size_t)n * batch * sizeof(fr)); }
+    CHK(prepare_shared_table(ks, mapped ? batch : chunk));   // (pageable input: the walks below see `chunk` rows at a time)
     dev_guard g(ks->fs);
     hipStream_t s = ks->fs->stream;
     dtmp<fr> d_sc(s); dtmp<g1j> d_out(s);
     CHK(d_out.alloc(batch));
     // Pinned input (kzg_hip_host_register, hipHostMalloc): the walk reads the coefficients IN PLACE over PCIe -- each scalar is loaded exactly once, 128 KiB per
     // blob = 13 GB/s at 100 k commitments/s -- instead of waiting for a staged copy of pageable memory (the calling thread copies at ~10 GB/s: 67-78 k/s)
-    if (const fr *mapped = (const fr *)host_mapped_pointer(coeffs_fr, (size_t)n * batch * sizeof(fr))) {
-        CHK(commit_rows(ks, s, mapped, n, batch, d_out.p));
+    if (mapped) {
+        CHK(commit_rows(ks, s, mapped, n, batch, d_out.p, 0, true, true));
         HIPCHK(hipMemcpyAsync(out_g1, d_out.p, batch * sizeof(g1j), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return KZG_HIP_OK;
     }
     CHK(d_sc.alloc(n * batch));
-    // Large batches are uploaded in chunks on a second stream: the copy of chunk i + 1 (from pageable host memory it occupies the
-    // calling thread) runs while the GPU walks chunk i.  Chunks keep >= 256 blobs so that a walk still fills one round of waves.
-    uint64_t chunk = batch >= 1024 ? 512 : (batch >= 512 ? 256 : batch);
-    if (chunk < batch && n * sizeof(fr) >= (64u << 10)) {
+    if (chunk < batch) {
         if (!ks->copy_stream) {
             HIPCHK(hipStreamCreateWithFlags(&ks->copy_stream, hipStreamNonBlocking));
             stream_cache_own(ks->copy_stream);
             for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&ks->copy_done[i], hipEventDisableTiming));
         }
-        CHK(ensure_fixed_table(ks, s));
+        CHK(ensure_fixed_table(ks, s));                      // (the ramp's first chunks walk it even where the full ones take the shared table)
         HIPCHK(hipStreamSynchronize(s));                     // d_sc was allocated in order on s: make it visible to the copy stream
         // The copy of the FIRST chunk overlaps with nothing, so the schedule ramps up: 64 blobs, then 192, then `chunk` at a time (KZG_HIP_UPLOAD_RAMP=0: equal
         // chunks, as through round 5) -- the walk starts after 8 MiB instead of 64 MiB of pageable copy.
@@ -269,11 +397,11 @@ int kzg_hip_commit_to_poly_batch(kzg_hip_kzg *ks, const void *coeffs_fr, uint64_
             CHK(h2d_copy(d_sc.p + b0 * n, (const fr *)coeffs_fr + b0 * n, n * cnt * sizeof(fr), ks->copy_stream));
             HIPCHK(hipEventRecord(ks->copy_done[slot], ks->copy_stream));
             HIPCHK(hipStreamWaitEvent(s, ks->copy_done[slot], 0));
-            CHK(commit_rows(ks, s, d_sc.p + b0 * n, n, cnt, d_out.p + b0));
+            CHK(commit_rows(ks, s, d_sc.p + b0 * n, n, cnt, d_out.p + b0, 0, true, true));
         }
     } else {
         CHK(h2d_copy(d_sc.p, coeffs_fr, n * batch * sizeof(fr), s));
-        CHK(commit_rows(ks, s, d_sc.p, n, batch, d_out.p));
+        CHK(commit_rows(ks, s, d_sc.p, n, batch, d_out.p, 0, true, true));
     }
     HIPCHK(hipMemcpyAsync(out_g1, d_out.p, batch * sizeof(g1j), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -523,12 +651,13 @@ int kzg_hip_toeplitz_part3(kzg_hip_kzg *ks, const void *h_ext_fft_g1, uint64_t n
     KZG_CATCH
 }
 
-// shape of the fixed-base table (window bits, windows, bytes); zeros before the first commitment or when no table fits
+// shape of the fixed-base table (window bits, windows, bytes): the all-window table while one exists, else the shared-window table of large batches
+// (its windows are per GLV half; its bytes hold one window); zeros before the first commitment or when no table fits
 int kzg_hip_kzg_table_info(kzg_hip_kzg *ks, uint32_t *window_bits, uint32_t *windows, uint64_t *table_bytes) {
     if (!ks || !window_bits || !windows || !table_bytes) return KZG_HIP_ERR_BAD_ARG;
-    bool have = ks->d_fixed != nullptr;
-    *window_bits = have ? ks->fixed_plan.c : 0; *windows = have ? ks->fixed_plan.nwin : 0;
-    *table_bytes = have ? (uint64_t)ks->fixed_plan.nwin * ks->fixed_plan.table_n * ks->fixed_plan.nb * sizeof(g1a) : 0;
+    const msm_plan *p = ks->d_fixed ? &ks->fixed_plan : ks->d_shared ? &ks->shared_plan : nullptr;   // the all-window table while one exists, else the shared-window one
+    *window_bits = p ? p->c : 0; *windows = p ? p->nwin : 0;
+    *table_bytes = p ? (uint64_t)(ks->d_fixed ? p->nwin : 1) * p->table_n * p->nb * sizeof(g1a) : 0;
     return KZG_HIP_OK;
 }
 // The reference's G1Point IS a Jacobian triple (bls/bls_kilic.go:30-35) and CommitToPoly / ComputeProofSingle return whatever Z their additions left; this
@@ -543,6 +672,7 @@ int kzg_hip_kzg_set_projective_outputs(kzg_hip_kzg *ks, int on) {
 }
 // mixed additions per coefficient of a commitment on that table: 2 x windows when both GLV halves of a scalar walk it (the default), else windows; 0 without a table
 uint32_t kzg_hip_kzg_table_additions(kzg_hip_kzg *ks) {
-    if (!ks || !ks->d_fixed) return 0;
+    if (!ks || (!ks->d_fixed && !ks->d_shared)) return 0;
+    if (!ks->d_fixed) return 2 * ks->shared_plan.nwin;     // the shared-window table: one entry per window and GLV half
     return ks->fixed_plan.glv ? 2 * ks->fixed_plan.nwin : ks->fixed_plan.nwin;
 }

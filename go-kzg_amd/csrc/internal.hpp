@@ -155,6 +155,13 @@ size_t fb_partials_bytes(uint64_t n, uint64_t batch);
 hipError_t launch_fb_build(hipStream_t s, const g1a *pts, uint64_t n, uint32_t c, uint32_t nwin, g1a *table);
 void launch_fb_msm(hipStream_t s, const g1a *table, uint64_t table_n, uint32_t c, uint32_t nwin, const fr *scalars, uint64_t sc_stride, uint64_t n,
                    uint64_t batch, void *partials, g1j *out, bool to_kilic, bool glv = false, bool projective = false);
+// the shared-window layout for large batches (k_msm.hip): table[i D + d - 1] = d P_i, W = ceil(128 / c) accumulators per blob, joined by a Horner finish.
+// The workspace holds the digit words of the pre-pass and the per-window partial sums.
+inline uint32_t fb_shared_windows(uint32_t c) { return (128 + c - 1) / c; }
+size_t fb_shared_workspace_bytes(uint64_t n, uint64_t batch, uint32_t c);
+hipError_t launch_fb_build_shared(hipStream_t s, const g1a *pts, uint64_t n, uint32_t c, g1a *table);
+void launch_fb_msm_shared(hipStream_t s, const g1a *table, uint32_t c, const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, void *workspace, g1j *out,
+                          bool to_kilic, bool projective);
 
 // out[(b, f, jj)] = scalars[b][f * row + j0 + jj] * P[f * row + j0 + jj] over a fixed-base table of table_n = nfiles * row points
 // (glv, here and below: the table holds ceil(128 / c) windows and both GLV halves of every scalar walk them)

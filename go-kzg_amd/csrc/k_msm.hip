@@ -379,38 +379,48 @@ __global__ __launch_bounds__(MSM_NB) void k_msm_reduce_chunks(uint8_t *ws, size_
 // Horner over the window groups (8 doublings per group), then normalise and convert.  The doublings are the critical path of a
 // lone MSM (120 for 16 groups, 56 for 8).  Quad form (g1_quad.hpp): the four LANES of a quad hold the replicas and exchange the products of a
 // level by DPP broadcasts -- no LDS, no barrier (a level 1.3 us instead of 1.84 with four wavefronts exchanging through LDS).  64 blobs per 256-lane workgroup.
-__global__ __launch_bounds__(256) void k_msm_combine(uint8_t *ws, size_t per_blob, size_t gsum_off, uint32_t ngroups, uint64_t batch, g1j *out, int to_kilic) {
-    const uint32_t role = threadIdx.x & 3u;
-    const uint64_t b = blockIdx.x * 64ull + (threadIdx.x >> 2);
-    const bool live = b < batch;
-    const fb_partial *gsum = (const fb_partial *)(ws + (live ? b : 0) * per_blob + gsum_off);
+// (quad_horner_finish: the loop and the ending, shared with the finish of the shared-window table walk, k_fb_finish_shared: there a group is a window
+// of c bits that holds `per_group` partial sums, one per workgroup of the blob.  fin: bit 0 Kilic images, bit 1 projective outputs -- no inversion.)
+__device__ __forceinline__ void quad_horner_finish(const fb_partial *sums, uint32_t ngroups, uint32_t ndbl, uint32_t per_group, bool live, uint32_t role, g1j *dst, int fin) {
     g1x_acc acc; acc.init();
     acc.v = g1xq_from_affine(g1a_inf());                   // defined limbs while the accumulator is still empty (results are discarded)
 #pragma nounroll
     for (uint32_t g = ngroups; g-- > 0;) {
 #pragma nounroll
-        for (uint32_t j = 0; j < 8; j++) {                 // every lane runs the doubling, empty accumulators ignore it
+        for (uint32_t j = 0; j < ndbl; j++) {              // every lane runs the doubling, empty accumulators ignore it
             g1xq d = acc.v;
             quad_xyzz_dbl(d, role);
             if (!acc.inf) acc.v = d;
         }
-        const bool winf = !live || gsum[g].inf != 0;
-        g1xq w;
-        if (winf) w = acc.v; else fb_partial_load(gsum[g], w);
-        quad_acc_add(acc, w, winf, role);
+#pragma nounroll
+        for (uint32_t j = 0; j < per_group; j++) {
+            const fb_partial &pj = sums[(uint64_t)g * per_group + j];
+            const bool winf = !live || pj.inf != 0;
+            g1xq w;
+            if (winf) w = acc.v; else fb_partial_load(pj, w);
+            quad_acc_add(acc, w, winf, role);
+        }
     }
     {   // x = X / ZZ, y = Y / ZZZ with one inversion per blob; a wavefront with up to three live blobs (a lone LinCombG1: one) inverts them cooperatively over its
         // lanes, a full one (16 blobs) in its lanes side by side (wave_inv_any decides; every lane of the wavefront is here)
         const bool own = live && role == 0;
         const g1x px = g1xq_pack(acc.v);
-        const fp i = wave_inv_any(mul(px.zz, px.zzz), own && !acc.inf);
+        const fp i = wave_inv_any(mul(px.zz, px.zzz), own && !acc.inf && !(fin & 2));
         if (own) {
             g1j r;
             if (acc.inf) r = g1_inf();
+            else if (fin & 2) r = g1x_to_jac(px);          // projective output: (X ZZ, Y ZZZ, ZZ)
             else { r.x = mul(px.x, mul(i, px.zzz)); r.y = mul(px.y, mul(i, px.zz)); r.z = one<FpP>(); }
-            out[b] = to_kilic ? g1_to_kilic(r) : r;
+            *dst = (fin & 1) ? g1_to_kilic(r) : r;
         }
     }
+}
+__global__ __launch_bounds__(256) void k_msm_combine(uint8_t *ws, size_t per_blob, size_t gsum_off, uint32_t ngroups, uint64_t batch, g1j *out, int to_kilic) {
+    const uint32_t role = threadIdx.x & 3u;
+    const uint64_t b = blockIdx.x * 64ull + (threadIdx.x >> 2);
+    const bool live = b < batch;
+    const fb_partial *gsum = (const fb_partial *)(ws + (live ? b : 0) * per_blob + gsum_off);
+    quad_horner_finish(gsum, ngroups, 8, 1, live, role, out + (live ? b : 0), to_kilic ? 1 : 0);
 }
 
 void launch_msm(hipStream_t s, const msm_plan &p, const g1a *table, const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, void *workspace, g1j *out,
@@ -806,6 +816,116 @@ __global__ __launch_bounds__(64) void k_fb_finish_lanes(const fb_partial *partia
     out[b] = (to_kilic & 1) ? g1_to_kilic(r) : r;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The SHARED-WINDOW layout for large batches.  The table above stores d 2^(c w) P_i for every window w so that all windows of a blob can share one
+// accumulator.  The factors 2^(c w) are not needed per entry:  sum_i d_(i,w) 2^(c w) P_i = 2^(c w) A_w  with  A_w = sum_i d_(i,w) P_i,  so a walk that keeps one
+// accumulator PER WINDOW needs the multiples d P_i alone -- T_s[i D + d - 1] = d P_i, which is launch_fb_build with nwin = 1 -- and the same HBM holds wider
+// digits: 103 GB are 4096 x 2^18 entries, signed 19-bit digits, 7 windows per GLV half = 14 additions per coefficient where the all-window table gives 16.
+// The window sums are joined once per blob, sum_w 2^(c w) A_w, by the Horner loop of k_msm_combine: c (W - 1) doublings of pure latency (~0.6 ms per launch,
+// whatever the batch), which is why only large batches take this path (capi_kzg.hip decides).
+//   k_fb_digits            : one lane per (blob, coefficient) splits the scalar once and writes the 2 W signed digits of its halves as words
+//                            (bits 0..19 the magnitude 0 .. D, bit 31 negate = digit sign ^ half sign) at digits[blob][half][w][i]; half 0 is the phi half
+//   k_fb_accumulate_shared : a lane owns ONE window for its whole life (one accumulator, the register budget of the walk above); the four lanes of a quad share
+//                            a window, Q = floor(64 / W) quads per window (W = 7: 63 quads work, one idles); the 4 Q lanes of a window divide the
+//                            workgroup's coefficients among themselves, sum their phi digits, map (X <- beta X), then their plain digits
+//   k_fb_finish_shared     : one quad per blob: Horner over the windows, then normalise
+// ---------------------------------------------------------------------------------------------------------
+#define FB_DIGIT_MAG 0xfffffu
+__global__ __launch_bounds__(256) void k_fb_digits(const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, uint32_t c, uint32_t W, uint32_t *digits) {
+    const uint64_t t = blockIdx.x * 256ull + threadIdx.x;
+    if (t >= n * batch) return;
+    const uint64_t blob = t / n, i = t % n;
+    const glv_halves h = glv_split_signed(from_mont<FrP>(scalars[blob * sc_stride + i]));
+    const uint32_t D = 1u << (c - 1);
+#pragma unroll
+    for (uint32_t half = 0; half < 2; half++) {
+        uint32_t m[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) m[j] = half ? h.k1[j] : h.k2[j];
+        const uint32_t sgn = (half ? h.neg1 : h.neg2) ? 1u : 0u;
+        uint32_t *dst = digits + ((blob * 2 + half) * W) * n + i;
+        uint32_t carry = 0;
+#pragma nounroll
+        for (uint32_t w = 0; w < W; w++) {                 // c W >= 128 and both halves are below 2^126.5: the top digit never carries out
+            const uint32_t raw = mag_bits(m, w * c, c) + carry;
+            uint32_t mag, ng;
+            if (raw > D) { carry = 1; mag = (1u << c) - raw; ng = 1; } else { carry = 0; mag = raw; ng = 0; }
+            dst[(uint64_t)w * n] = mag ? (mag | ((ng ^ sgn) << 31)) : 0u;
+        }
+    }
+}
+__global__ __launch_bounds__(FB_ACC_BLOCK, FB_ACC_WAVES) void k_fb_accumulate_shared(const g1a *table, uint32_t D, uint32_t W, uint32_t Q, const uint32_t *digits, uint64_t n,
+                                                                                   uint32_t blocks_per_blob, fb_partial *partials) {
+    __shared__ fb_partial buf[64];
+    const uint32_t tid = threadIdx.x, role = tid & 3u, quad = tid >> 2;
+    const uint64_t blob = blockIdx.x / blocks_per_blob; const uint32_t blk = blockIdx.x % blocks_per_blob;
+    const bool live = quad < W * Q;                       // (quad-uniform)
+    const uint32_t w = live ? quad / Q : 0u;
+    const uint32_t LW = 4 * Q;                            // lanes of one window
+    g1x_acc acc; acc.init();
+    if (live) {
+        // lane j of its window takes the coefficients (t blocks_per_blob + blk) LW + j: the lanes of a window read neighbouring digit words
+        const uint64_t stride = (uint64_t)blocks_per_blob * LW;
+        const uint64_t i0 = (uint64_t)blk * LW + (tid - w * LW);
+        const uint64_t cnt = i0 < n ? (n - i0 + stride - 1) / stride : 0;
+        const uint32_t *dphi = digits + ((blob * 2) * W + w) * n, *dplain = dphi + (uint64_t)W * n;
+        const uint64_t K = 2 * cnt;                       // steps: the phi digits of the lane's coefficients, then the plain ones
+        if (K) {
+            // software pipeline: the digit word of step k + 2 and the gather of step k + 1 are issued before the addition of step k
+            uint32_t wc = dphi[i0];
+            g1a qn = table[i0 * D + ((wc & FB_DIGIT_MAG) ? (wc & FB_DIGIT_MAG) - 1 : 0)];
+            uint32_t wn = cnt > 1 ? dphi[i0 + stride] : dplain[i0];
+#pragma nounroll
+            for (uint64_t k = 0; k < K; k++) {
+                const g1a q0 = qn;
+                const uint32_t cur = wc;
+                wc = wn;
+                if (k + 1 < K) {
+                    const uint64_t i1 = i0 + (k + 1 < cnt ? k + 1 : k + 1 - cnt) * stride;
+                    qn = table[i1 * D + ((wc & FB_DIGIT_MAG) ? (wc & FB_DIGIT_MAG) - 1 : 0)];
+                }
+                if (k + 2 < K) wn = k + 2 < cnt ? dphi[i0 + (k + 2) * stride] : dplain[i0 + (k + 2 - cnt) * stride];
+                if (k == cnt && !acc.inf) acc.v.x = mulq(acc.v.x, unpackq(glv_beta()));   // the lane crosses into its plain digits: map the phi sum
+                if (cur & FB_DIGIT_MAG) {
+                    g1a q = q0;
+                    if (cur >> 31) q.y = neg<FpP>(q.y);
+                    acc.add(q);
+                }
+            }
+        }
+    }
+    // block end: W sums.  The four accumulators of a quad first (DPP, as fb_block_reduce_quad), then the Q quads of a window through LDS: every quad of the
+    // window runs the same serial chain over the window's Q columns (no divergence inside a wavefront) and its first quad stores the sum.  Q - 1 <= 8 additions
+    // of ~6 us against a workgroup life of milliseconds.
+    if (acc.inf) acc.v = g1xq_from_affine(g1a_inf());      // defined limbs in empty accumulators (their additions are computed and dropped)
+    const uint32_t ainf = acc.inf ? 1u : 0u;
+    g1x_acc col;
+    { uint32_t vi; quad_point_bcast<0>(col.v, vi, acc.v, ainf); col.inf = vi != 0; }
+    { g1xq v; uint32_t vi; quad_point_bcast<1>(v, vi, acc.v, ainf); quad_tree_add(col, v, vi != 0, role); }
+    { g1xq v; uint32_t vi; quad_point_bcast<2>(v, vi, acc.v, ainf); quad_tree_add(col, v, vi != 0, role); }
+    { g1xq v; uint32_t vi; quad_point_bcast<3>(v, vi, acc.v, ainf); quad_tree_add(col, v, vi != 0, role); }
+    if (col.inf) col.v = g1xq_from_affine(g1a_inf());
+    if (role == 0) fb_partial_store(buf[quad], col);
+    __syncthreads();
+    const uint32_t base = live ? w * Q : quad;             // idle quads chain over their own (empty) column
+    g1x_acc sum;
+    fb_partial_load(buf[base], sum.v); sum.inf = buf[base].inf != 0;
+#pragma nounroll
+    for (uint32_t j = 1; j < Q; j++) {
+        const fb_partial &src = buf[live ? base + j : quad];
+        g1xq v; fb_partial_load(src, v);
+        quad_tree_add(sum, v, !live || src.inf != 0, role);
+    }
+    if (live && quad == base && role == 0) fb_partial_store(partials[(blob * W + w) * blocks_per_blob + blk], sum);
+}
+// one quad per blob, 64 blobs per 256-lane workgroup (the shape of k_msm_combine): for w = W - 1 .. 0: c doublings, then the blocks_per_blob partial sums of window w
+__global__ __launch_bounds__(256) void k_fb_finish_shared(const fb_partial *partials, uint32_t c, uint32_t W, uint32_t blocks_per_blob, uint64_t batch, g1j *out, int fin) {
+    const uint32_t role = threadIdx.x & 3u;
+    const uint64_t b = blockIdx.x * 64ull + (threadIdx.x >> 2);
+    const bool live = b < batch;
+    quad_horner_finish(partials + (live ? b : 0) * W * blocks_per_blob, W, c, blocks_per_blob, live, role, out + (live ? b : 0), fin);
+}
+
 // One fixed-base product added into an accumulator: the walk of point i's rows with the signed c-bit digits of a scalar (standard form), sign sg folded in.
 //   GLV = false: the plain layout, nwin windows over the whole scalar (phi is ignored, one call per term);
 //   GLV = true : the table holds ceil(128 / c) windows; the call walks ONE half of the split scalar -- phi ? |k2| : |k1| -- so a caller sums the phi halves of all
@@ -1074,6 +1194,44 @@ void launch_fb_msm(hipStream_t s, const g1a *table, uint64_t table_n, uint32_t c
     prof_end(s, "fb_accumulate");
     if (bpb <= FB_FINISH_LANES_MAX) hipLaunchKernelGGL(k_fb_finish_lanes, dim3((uint32_t)((batch + 63) / 64)), dim3(64), 0, s, (const fb_partial *)partials, bpb, batch, out, fin);
     else hipLaunchKernelGGL(k_fb_finish, dim3((uint32_t)batch), dim3(256), 0, s, (const fb_partial *)partials, bpb, batch, out, fin);
+}
+// The shared-window walk (k_fb_accumulate_shared): workgroups per blob as above, but never more than give every lane of a window a coefficient
+static uint32_t fb_shared_blocks_per_blob(uint64_t n, uint64_t batch, uint32_t W) {
+    const uint32_t LW = 4 * (64 / W);
+    const uint64_t maxb = (n + LW - 1) / LW;
+    const uint64_t bpb = fb_blocks_per_blob(2 * n, batch);
+    return (uint32_t)(bpb > maxb ? maxb : bpb);
+}
+static size_t fb_shared_digit_bytes(uint64_t n, uint64_t batch, uint32_t W) { return (((size_t)batch * 2 * W * n * sizeof(uint32_t)) + 15) / 16 * 16; }
+size_t fb_shared_workspace_bytes(uint64_t n, uint64_t batch, uint32_t c) {
+    const uint32_t W = fb_shared_windows(c);
+    return fb_shared_digit_bytes(n, batch, W) + (((size_t)fb_shared_blocks_per_blob(n, batch, W) * W * batch * sizeof(fb_partial)) + 15) / 16 * 16;
+}
+// table[i D + d - 1] = d P_i, D = 2^(c-1), 5 <= c <= 20: the digit pre-pass, the walk (one accumulator per window), the Horner finish
+void launch_fb_msm_shared(hipStream_t s, const g1a *table, uint32_t c, const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, void *workspace, g1j *out,
+                          bool to_kilic, bool projective) {
+    if (!batch) return;
+    const uint32_t W = fb_shared_windows(c), Q = 64 / W;
+    const uint32_t bpb = fb_shared_blocks_per_blob(n, batch, W);
+    uint32_t *digits = (uint32_t *)workspace;
+    fb_partial *partials = (fb_partial *)((uint8_t *)workspace + fb_shared_digit_bytes(n, batch, W));
+    hipLaunchKernelGGL(k_fb_digits, dim3((uint32_t)((n * batch + 255) / 256)), dim3(256), 0, s, scalars, sc_stride, n, batch, c, W, digits);
+    prof_begin(s, "fb_accumulate");
+    hipLaunchKernelGGL(k_fb_accumulate_shared, dim3((uint32_t)(batch * bpb)), dim3(FB_ACC_BLOCK), 0, s, table, 1u << (c - 1), W, Q, digits, n, bpb, partials);
+    prof_end(s, "fb_accumulate");
+    hipLaunchKernelGGL(k_fb_finish_shared, dim3((uint32_t)((batch + 63) / 64)), dim3(256), 0, s, (const fb_partial *)partials, c, W, bpb, batch, out,
+                       (to_kilic ? 1 : 0) | (projective ? 2 : 0));
+}
+// the shared-window table of `n` points: launch_fb_build with one window, in slices of points so that its temporaries stay near 2 x 1 GiB at every digit width
+hipError_t launch_fb_build_shared(hipStream_t s, const g1a *pts, uint64_t n, uint32_t c, g1a *table) {
+    const uint64_t D = 1ull << (c - 1);
+    uint64_t slice = (1ull << 30) / (D * sizeof(fp));
+    if (slice < 1) slice = 1;
+    for (uint64_t i0 = 0; i0 < n; i0 += slice) {
+        const hipError_t e = launch_fb_build(s, pts + i0, n - i0 < slice ? n - i0 : slice, c, 1, table + i0 * D);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 // builds the table for `n` affine points: rows (2^(c w) P_i) first, then all multiples window-slab by window-slab
 hipError_t launch_fb_build(hipStream_t s, const g1a *pts, uint64_t n, uint32_t c, uint32_t nwin, g1a *table) {

@@ -33,6 +33,7 @@ enum class transcript_mode { by_count, host, device };
 enum class pairing_mode { by_count, lane, wave };
 enum class combine_mode { by_count, never, always };
 enum class transport_mode { by_devices, rccl, host, peer };
+enum class fb_layout_mode { by_batch, windows, shared };
 struct opt_gb { bool set; double gb; };   // a table budget: unset leaves the size to the caller's policy
 
 // ---- grammar
@@ -94,6 +95,7 @@ KZG_KNOB_ONCE(int, msm_seg, "KZG_HIP_MSM_SEG", e ? atoi(e) : -1)                
 KZG_KNOB_PER_CALL(transcript_mode, eth_transcript, "KZG_HIP_ETH_TRANSCRIPT", is(e, "host") ? transcript_mode::host : is(e, "device") ? transcript_mode::device : transcript_mode::by_count)   // where the aggregate verifier and the batched aggregate prover hash
 KZG_KNOB_PER_CALL(pairing_mode, pairing, "KZG_HIP_PAIRING", is(e, "lane") ? pairing_mode::lane : is(e, "wave") ? pairing_mode::wave : pairing_mode::by_count)   // the kernel of every pairing check: one lane or one wavefront per check (launch_pairing_check; tests, A/B runs)
 KZG_KNOB_PER_CALL(combine_mode, verify_combine, "KZG_HIP_VERIFY_COMBINE", is(e, "never") ? combine_mode::never : is(e, "always") ? combine_mode::always : combine_mode::by_count)   // the _combined proof checks: per-row checks or one check per group of rows at every count (capi_verify.hip; tests, A/B runs)
+KZG_KNOB_PER_CALL(fb_layout_mode, fb_layout, "KZG_HIP_FB_LAYOUT", is(e, "windows") ? fb_layout_mode::windows : is(e, "shared") ? fb_layout_mode::shared : fb_layout_mode::by_batch)   // commitment tables: "windows" never builds or walks the shared-window table, "shared" walks it at every batch size; anything else ("auto"): large batches only (capi_kzg.hip)
 KZG_KNOB_PER_CALL(int, multi_fft, "KZG_HIP_MULTI_FFT", !e ? -1 : is(e, "sharded") ? 1 : 0)                                                   // -1 the handle's policy; "sharded" 1; ANY other value gathers (0)
 KZG_KNOB_PER_HANDLE(transport_mode, multi_transport, "KZG_HIP_MULTI_TRANSPORT", !e ? transport_mode::by_devices : is(e, "rccl") ? transport_mode::rccl : is(e, "host") ? transport_mode::host : transport_mode::peer)   // any other value: peer copies, RCCL is not bound
 KZG_KNOB_PER_HANDLE(unsigned, multi_fault, "KZG_HIP_MULTI_FAULT", multi_fault_of(e))                                                        // tests: a comma-separated list of legs of the exchange that fail, FAULT_* above
@@ -103,6 +105,7 @@ KZG_KNOB_ONCE(const char *, rccl_lib, "KZG_HIP_RCCL_LIB", e)                    
 KZG_KNOB_ONCE(uint32_t, lincomb_promote_after, "KZG_HIP_LINCOMB_PROMOTE_AFTER", (uint32_t)(!e ? 2 : atol(e) < 1 ? 1 : atol(e) > 1000 ? 1000 : atol(e)))   // sightings before a point set is promoted: 1 .. 1000
 KZG_KNOB_ONCE(uint64_t, fb_lanes, "KZG_HIP_FB_LANES", e ? strtoull(e, nullptr, 10) : 0ull)                                                  // lanes of one table-walk launch; 0: two resident waves per SIMD
 KZG_KNOB_ONCE(uint64_t, eth_stage_rows, "KZG_HIP_ETH_STAGE_ROWS", e ? (uint64_t)atol(e) : 0ull)                                             // coalesced eth proof batches of up to this many rows are copied to HBM first (A/B runs, tests)
+KZG_KNOB_PER_CALL(uint64_t, fb_shared_min_batch, "KZG_HIP_FB_SHARED_MIN_BATCH", e && strtoull(e, nullptr, 10) >= 1 ? strtoull(e, nullptr, 10) : 0ull)                    // rows from which a commitment batch walks the shared-window table, at least 1; 0 (unset, or no such number): the library's measured crossovers
 KZG_KNOB_PER_CALL(uint64_t, verify_combine_rows, "KZG_HIP_VERIFY_COMBINE_ROWS", e && strtoull(e, nullptr, 10) >= 1 ? strtoull(e, nullptr, 10) : 0ull)                  // rows per group of the _combined proof checks, at least 1; 0 (unset, or no such number): the library's group size
 KZG_KNOB_PER_CALL(double, eth_verify_chunk_mb, "KZG_HIP_ETH_VERIFY_CHUNK_MB", positive_or(e, 4096.0))                                      // blob bytes per chunk of the aggregate verifier; fractions allowed, <= 0 is the default
 KZG_KNOB_PER_CALL(double, eth_prove_chunk_mb, "KZG_HIP_ETH_PROVE_CHUNK_MB", positive_or(e, 4096.0))                                        // device bytes per chunk of the batched aggregate prover (twice a sidecar's blob bytes + two rows); likewise

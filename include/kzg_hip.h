@@ -474,7 +474,11 @@ int kzg_hip_multi_da_using_fk20_multi(kzg_hip_multi_fk20m *fk, const void *poly_
 /* shape of the fixed-base table CommitToPoly walks (built lazily by the first commitment): signed window bits c, window count and
  * bytes of HBM; all zero before the first commitment or when the setup is too small for a table (classic bucket path).  Both GLV halves of a
  * scalar (k = k1 + k2 lambda, |k1|, |k2| < 2^127) walk the same rows, so `windows` = ceil(128 / c) and a coefficient costs 2 x windows mixed
- * additions (kzg_hip_kzg_table_additions): 4096 points at c = 16 are 8 windows = 103 GB, the default budget (110 GB; kzg_hip_kzg_set_table_budget_gb). */
+ * additions (kzg_hip_kzg_table_additions): 4096 points at c = 16 are 8 windows = 103 GB, the default budget (110 GB; kzg_hip_kzg_set_table_budget_gb).
+ * Batches of 2048 rows and more (kzg_hip_commit_to_poly_batch, _dev) walk a second, shared-window table d P_i paid from the same budget (one accumulator per window, joined
+ * per blob: 19-bit digits, 7 windows, 14 additions from the same 103 GB); where the budget cannot hold both and the shared table needs fewer additions it replaces the
+ * all-window table, and later small calls get the all-window table the remainder affords.  These two calls describe the all-window table while one exists, otherwise the
+ * shared one: window bits, windows per GLV half, bytes; 2 x windows additions.  KZG_HIP_FB_LAYOUT=windows keeps every batch on the all-window table. */
 int kzg_hip_kzg_table_info(kzg_hip_kzg *ks, uint32_t *window_bits, uint32_t *windows, uint64_t *table_bytes);
 uint32_t kzg_hip_kzg_table_additions(kzg_hip_kzg *ks);
 /* Projective outputs (off by default).  The reference's G1Point is a Jacobian triple and CommitToPoly / ComputeProofSingle return it with whatever Z the
