@@ -231,6 +231,12 @@ template <class T> struct dtmp {
     }
     ~dtmp() { if (p && !(cls && stream_cache_give(s, p, cls))) hipFreeAsync(p, s); }
 };
+// a temporary that only receives one host array of `count` elements: allocated, then filled on its stream
+template <class T> int upload(dtmp<T> &d, const void *host, size_t count) {
+    CHK(d.alloc(count));
+    HIPCHK(hipMemcpyAsync(d.p, host, count * sizeof(T), hipMemcpyHostToDevice, d.s));
+    return KZG_HIP_OK;
+}
 
 // (ROCm maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues, default 4: kernels of streams that share a queue run one after
 // the other.  Measured with 16 host threads of FFT_Fr(4096) on host buffers: x3.9 of one thread with 4 queues, x5.4 with 8, x5.6 with 16 --

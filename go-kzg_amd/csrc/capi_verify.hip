@@ -30,8 +30,7 @@ namespace {
 
 int prepare_points(hipStream_t s, const g2j *h_kilic, uint64_t n, g2_prepared *d_out) {
     dtmp<g2j> d_in(s);
-    CHK(d_in.alloc(n));
-    HIPCHK(hipMemcpyAsync(d_in.p, h_kilic, n * sizeof(g2j), hipMemcpyHostToDevice, s));
+    CHK(upload(d_in, h_kilic, n));
     launch_g2_prepare(s, d_in.p, n, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
@@ -109,8 +108,7 @@ int g2_mul_generator(kzg_hip_fft *fs, const void *scalars_fr, bool powers_of_one
     dtmp<g2j> d_a(s), d_b(s); dtmp<fr> d_k(s), d_s(s);
     CHK(d_a.alloc(n)); CHK(d_b.alloc(n)); CHK(d_k.alloc(n));
     if (powers_of_one) {
-        CHK(d_s.alloc(1));
-        HIPCHK(hipMemcpyAsync(d_s.p, scalars_fr, sizeof(fr), hipMemcpyHostToDevice, s));
+        CHK(upload(d_s, scalars_fr, 1));
         launch_fr_powers(s, d_s.p, n, d_k.p);
     } else {
         HIPCHK(hipMemcpyAsync(d_k.p, scalars_fr, n * sizeof(fr), hipMemcpyHostToDevice, s));
@@ -127,14 +125,8 @@ int g2_mul_generator(kzg_hip_fft *fs, const void *scalars_fr, bool powers_of_one
 int kzg_checks(hipStream_t s, const g2_prepared *gen, const g2_prepared *q1, const void *c_g1, const void *pi_g1, const void *ys_fr, const g1j *d_es,
                const void *bs_fr, const fr *d_bs, uint64_t count, uint8_t *ok) {
     dtmp<g1j> d_c(s), d_pi(s), d_p0(s), d_p1(s); dtmp<fr> d_y(s), d_b(s);
-    CHK(d_c.alloc(count)); CHK(d_pi.alloc(count)); CHK(d_p0.alloc(count)); CHK(d_p1.alloc(count));
-    HIPCHK(hipMemcpyAsync(d_c.p, c_g1, count * sizeof(g1j), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_pi.p, pi_g1, count * sizeof(g1j), hipMemcpyHostToDevice, s));
-    if (ys_fr) {
-        CHK(d_y.alloc(count)); CHK(d_b.alloc(count));
-        HIPCHK(hipMemcpyAsync(d_y.p, ys_fr, count * sizeof(fr), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_b.p, bs_fr, count * sizeof(fr), hipMemcpyHostToDevice, s));
-    }
+    CHK(upload(d_c, c_g1, count)); CHK(upload(d_pi, pi_g1, count)); CHK(d_p0.alloc(count)); CHK(d_p1.alloc(count));
+    if (ys_fr) { CHK(upload(d_y, ys_fr, count)); CHK(upload(d_b, bs_fr, count)); }
     launch_kzg_check_inputs(s, d_c.p, d_pi.p, ys_fr ? d_y.p : nullptr, d_es, ys_fr ? d_b.p : d_bs, count, d_p0.p, d_p1.p);
     HIPCHK(hipGetLastError());
     return run_shared_check(s, gen, q1, d_p0.p, d_p1.p, count, ok);
@@ -144,12 +136,8 @@ int kzg_checks(hipStream_t s, const g2_prepared *gen, const g2_prepared *q1, con
 int eth_checks(hipStream_t s, const g2_prepared *gen, const g2_prepared *q1, const void *commitments48, const void *zs_le32, const void *ys_le32, const void *proofs48,
                uint64_t count, uint8_t *result) {
     dtmp<uint8_t> d_c(s), d_z(s), d_y(s), d_pi(s), d_st(s), d_ok(s); dtmp<g1j> d_p0(s), d_p1(s);
-    CHK(d_c.alloc(48 * count)); CHK(d_pi.alloc(48 * count)); CHK(d_z.alloc(32 * count)); CHK(d_y.alloc(32 * count));
+    CHK(upload(d_c, commitments48, 48 * count)); CHK(upload(d_pi, proofs48, 48 * count)); CHK(upload(d_z, zs_le32, 32 * count)); CHK(upload(d_y, ys_le32, 32 * count));
     CHK(d_st.alloc(count)); CHK(d_ok.alloc(count)); CHK(d_p0.alloc(count)); CHK(d_p1.alloc(count));
-    HIPCHK(hipMemcpyAsync(d_c.p, commitments48, 48 * count, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_pi.p, proofs48, 48 * count, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_z.p, zs_le32, 32 * count, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_y.p, ys_le32, 32 * count, hipMemcpyHostToDevice, s));
     launch_eth_check_inputs(s, d_c.p, d_z.p, d_y.p, d_pi.p, count, d_p0.p, d_p1.p, d_st.p);
     // e(C - [y]G1 + [z] pi, G2) e(-pi, kzgSetupG2[1]) == 1  <=>  e(C - [y]G1, G2) == e(pi, [s - z]G2)  (eth/helpers.go:55-68)
     launch_pairing_check(s, true, gen, q1, d_p0.p, d_p1.p, count, d_ok.p);
@@ -171,7 +159,6 @@ constexpr uint64_t COMBINE_CHUNK_GROUPS = 1024;             // group checks per 
 constexpr uint64_t COMBINE_CHUNK_BYTES = 2048ull << 20;     // ... fewer when the groups' MSM workspaces would exceed this
 
 // what the last _combined call on this thread did (kzg_hip_test_combine_stats)
-struct combine_stats { uint64_t route, groups, failed, rechecked; };
 thread_local combine_stats t_combine;
 
 bool combine_route(uint64_t count) {
@@ -247,6 +234,13 @@ int combine_group_checks(hipStream_t s, const g2_prepared *gen, const g2_prepare
     launch_combine_negate(s, d_a, G, d_p1.p);
     return run_shared_check(s, gen, q1, d_b, d_p1.p, G, h_ok);
 }
+// one chunk of whole groups from host rows of CheckProofSingle: upload, sums.  d_a / d_b: G points
+int combine_single_chunk(hipStream_t s, const combine_seed &seed, const g1j *c, const g1j *pi, const fr *xs, const fr *ys, uint64_t row0, uint64_t k, uint64_t R, g1j *d_a,
+                         g1j *d_b, bool to_kilic) {
+    dtmp<g1j> d_c(s), d_pi(s); dtmp<fr> d_x(s), d_y(s);
+    CHK(upload(d_c, c, k)); CHK(upload(d_pi, pi, k)); CHK(upload(d_x, xs, k)); CHK(upload(d_y, ys, k));
+    return combine_group_sums(s, seed, d_c.p, d_pi.p, true, d_x.p, d_y.p, nullptr, row0, k, R, d_a, d_b, to_kilic);
+}
 
 // ---- the multi-proof form (verify_combine_multi.hpp, k_verify_combine_multi.hip) ----
 // KZGSettings.CheckProofMulti over `count` host rows of n values, one pairing check per row: IFFT(ys) per row, coefficients times x^-i, x^np,
@@ -255,9 +249,7 @@ int combine_group_checks(hipStream_t s, const g2_prepared *gen, const g2_prepare
 int multi_checks(kzg_hip_kzg *ks, hipStream_t s, const g2_prepared *gen, const g2_prepared *qn, const void *commitments_g1, const void *proofs_g1, const void *xs_fr,
                  const void *ys_fr, uint64_t n, uint64_t np, uint64_t count, uint8_t *ok) {
     dtmp<fr> d_ys(s), d_ip(s), d_x(s), d_xp(s); dtmp<g1j> d_is(s);
-    CHK(d_ys.alloc(count * n)); CHK(d_ip.alloc(count * np)); CHK(d_x.alloc(count)); CHK(d_xp.alloc(count)); CHK(d_is.alloc(count));
-    HIPCHK(hipMemcpyAsync(d_ys.p, ys_fr, count * n * sizeof(fr), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_x.p, xs_fr, count * sizeof(fr), hipMemcpyHostToDevice, s));
+    CHK(upload(d_ys, ys_fr, count * n)); CHK(upload(d_x, xs_fr, count)); CHK(d_ip.alloc(count * np)); CHK(d_xp.alloc(count)); CHK(d_is.alloc(count));
     fr_fft_rows(ks->fs, s, d_ys.p, n, n, d_ip.p, np, count, 1);
     launch_fr_rows_scale_by_inv_powers(s, d_ip.p, np, d_x.p, count, d_xp.p);
     CHK(commit_rows(ks, s, d_ip.p, np, count, d_is.p));
@@ -304,13 +296,18 @@ int combine_multi_group_sums(kzg_hip_kzg *ks, hipStream_t s, const combine_seed 
 int combine_multi_chunk(kzg_hip_kzg *ks, hipStream_t s, const combine_seed &seed, const g1j *c, const g1j *pi, const fr *xs, const fr *ys, uint64_t n, uint64_t np,
                         uint64_t row0, uint64_t k, uint64_t R, fr *d_j, g1j *d_a, g1j *d_b, bool to_kilic) {
     dtmp<g1j> d_c(s), d_pi(s); dtmp<fr> d_x(s), d_ys(s), d_ip(s);
-    CHK(d_c.alloc(k)); CHK(d_pi.alloc(k)); CHK(d_x.alloc(k)); CHK(d_ys.alloc(k * n)); CHK(d_ip.alloc(k * np));
-    HIPCHK(hipMemcpyAsync(d_c.p, c, k * sizeof(g1j), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_pi.p, pi, k * sizeof(g1j), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_x.p, xs, k * sizeof(fr), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_ys.p, ys, k * n * sizeof(fr), hipMemcpyHostToDevice, s));
+    CHK(upload(d_c, c, k)); CHK(upload(d_pi, pi, k)); CHK(upload(d_x, xs, k)); CHK(upload(d_ys, ys, k * n)); CHK(d_ip.alloc(k * np));
     fr_fft_rows(ks->fs, s, d_ys.p, n, n, d_ip.p, np, k, 1);
     return combine_multi_group_sums(ks, s, seed, d_c.p, d_pi.p, d_x.p, d_ip.p, np, row0, k, R, d_j, d_a, d_b, to_kilic);
+}
+// what both CheckProofMulti entries ask of a call with rows, in the per-row entry's order; *np = the padded length of a row's values
+int multi_batch_args(const kzg_hip_kzg *ks, const g2_state *g, const void *commitments_g1, const void *proofs_g1, const void *xs_fr, const void *ys_fr, const uint8_t *ok,
+                     uint64_t n, uint64_t *np) {
+    if (!commitments_g1 || !proofs_g1 || !xs_fr || !ys_fr || !ok || n == 0) return KZG_HIP_ERR_BAD_ARG;
+    if (n >= g->h_g2.size()) return KZG_HIP_ERR_LEN_MISMATCH;     // SecretG2[len(ys)]
+    if (n > ks->fs->W) return KZG_HIP_ERR_TOO_WIDE;              // "ys is bad, cannot compute FFT" panic, kzg_multi_proofs.go:50-53
+    *np = next_pow2(n);
+    return *np > ks->n_setup ? KZG_HIP_ERR_LEN_MISMATCH : KZG_HIP_OK;
 }
 
 }  // namespace
@@ -362,9 +359,8 @@ int kzg_hip_g2_from_compressed(kzg_hip_fft *fs, const void *in96, uint64_t n, vo
     stream_lease lease(fs);
     hipStream_t s = lease.s;
     dtmp<uint8_t> d_in(s); dtmp<g2j> d_out(s); dtmp<uint32_t> d_bad(s);
-    CHK(d_in.alloc(96 * n)); CHK(d_out.alloc(n)); CHK(d_bad.alloc(1));
+    CHK(upload(d_in, in96, 96 * n)); CHK(d_out.alloc(n)); CHK(d_bad.alloc(1));
     HIPCHK(hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
-    HIPCHK(hipMemcpyAsync(d_in.p, in96, 96 * n, hipMemcpyHostToDevice, s));
     launch_g2_from_compressed(s, d_in.p, d_out.p, n, d_bad.p);
     HIPCHK(hipGetLastError());
     uint32_t bad = 0;
@@ -396,8 +392,7 @@ int kzg_hip_g2_to_compressed(kzg_hip_fft *fs, const void *points_g2, uint64_t n,
     stream_lease lease(fs);
     hipStream_t s = lease.s;
     dtmp<g2j> d_in(s); dtmp<uint8_t> d_out(s);
-    CHK(d_in.alloc(n)); CHK(d_out.alloc(96 * n));
-    HIPCHK(hipMemcpyAsync(d_in.p, points_g2, n * sizeof(g2j), hipMemcpyHostToDevice, s));
+    CHK(upload(d_in, points_g2, n)); CHK(d_out.alloc(96 * n));
     launch_g2_compress(s, d_in.p, n, d_out.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out96, d_out.p, 96 * n, hipMemcpyDeviceToHost, s));
@@ -470,15 +465,11 @@ int kzg_hip_check_proof_multi_batch(kzg_hip_kzg *ks, const void *commitments_g1,
     const std::shared_ptr<g2_state> g = g2_of(ks->g2_mu, ks->g2);
     if (!g) return KZG_HIP_ERR_BAD_ARG;
     if (!count) return KZG_HIP_OK;
-    if (!commitments_g1 || !proofs_g1 || !xs_fr || !ys_fr || !ok || n == 0) return KZG_HIP_ERR_BAD_ARG;
-    if (n >= g->h_g2.size()) return KZG_HIP_ERR_LEN_MISMATCH;     // SecretG2[len(ys)]
-    kzg_hip_fft *fs = ks->fs;
-    if (n > fs->W) return KZG_HIP_ERR_TOO_WIDE;                  // "ys is bad, cannot compute FFT" panic, kzg_multi_proofs.go:50-53
-    const uint64_t np = next_pow2(n);
-    if (np > ks->n_setup) return KZG_HIP_ERR_LEN_MISMATCH;
+    uint64_t np = 0;
+    CHK(multi_batch_args(ks, g.get(), commitments_g1, proofs_g1, xs_fr, ys_fr, ok, n, &np));
     // all rows at once (kzg_hip_check_proof_multi_interpolation's steps over `count` rows, multi_checks)
-    dev_guard dg(fs);
-    hipStream_t s = fs->stream;
+    dev_guard dg(ks->fs);
+    hipStream_t s = ks->fs->stream;
     const g2_prepared *qn = nullptr;
     CHK(g2_pow(g.get(), s, n, &qn));
     return multi_checks(ks, s, g->d_gen, qn, commitments_g1, proofs_g1, xs_fr, ys_fr, n, np, count, ok);
@@ -494,41 +485,26 @@ int kzg_hip_check_proof_multi_batch_combined(kzg_hip_kzg *ks, const void *commit
     const std::shared_ptr<g2_state> g = g2_of(ks->g2_mu, ks->g2);
     if (!g) return KZG_HIP_ERR_BAD_ARG;
     if (!count) return KZG_HIP_OK;
-    if (!commitments_g1 || !proofs_g1 || !xs_fr || !ys_fr || !ok || n == 0) return KZG_HIP_ERR_BAD_ARG;
-    if (n >= g->h_g2.size()) return KZG_HIP_ERR_LEN_MISMATCH;
-    kzg_hip_fft *fs = ks->fs;
-    if (n > fs->W) return KZG_HIP_ERR_TOO_WIDE;
-    const uint64_t np = next_pow2(n);
-    if (np > ks->n_setup) return KZG_HIP_ERR_LEN_MISMATCH;
+    uint64_t np = 0;
+    CHK(multi_batch_args(ks, g.get(), commitments_g1, proofs_g1, xs_fr, ys_fr, ok, n, &np));
     t_combine = combine_stats{};
-    dev_guard dg(fs);
-    hipStream_t s = fs->stream;
+    dev_guard dg(ks->fs);
+    hipStream_t s = ks->fs->stream;
     const g2_prepared *qn = nullptr;
     CHK(g2_pow(g.get(), s, n, &qn));
     if (!combine_multi_route(n, count)) return multi_checks(ks, s, g->d_gen, qn, commitments_g1, proofs_g1, xs_fr, ys_fr, n, np, count, ok);
     t_combine.route = 1;
     const combine_seed seed = combine_seed_of(seed32);
-    const uint64_t R = combine_rows(), chunk = combine_multi_chunk_groups(R, n, np) * R;
+    const uint64_t R = combine_rows();
     const g1j *c = (const g1j *)commitments_g1, *pi = (const g1j *)proofs_g1; const fr *xs = (const fr *)xs_fr, *ys = (const fr *)ys_fr;
-    std::vector<uint8_t> gok;
-    for (uint64_t i0 = 0; i0 < count; i0 += chunk) {
-        const uint64_t k = count - i0 < chunk ? count - i0 : chunk, G = combine_group_count(k, R);
-        {
+    return combine_drive(count, R, combine_multi_chunk_groups(R, n, np) * R, ok, t_combine,
+        [&](uint64_t i0, uint64_t k, uint64_t G, uint8_t *, uint8_t *gok) -> int {
             dtmp<g1j> d_a(s), d_b(s); dtmp<fr> d_j(s);
             CHK(d_a.alloc(G)); CHK(d_b.alloc(G)); CHK(d_j.alloc(G * np));
             CHK(combine_multi_chunk(ks, s, seed, c + i0, pi + i0, xs + i0, ys + i0 * n, n, np, i0, k, R, d_j.p, d_a.p, d_b.p, false));
-            gok.assign(G, 0);
-            CHK(combine_group_checks(s, g->d_gen, qn, d_a.p, d_b.p, G, gok.data()));
-        }
-        t_combine.groups += G;
-        for (uint64_t gi = 0; gi < G; gi++) {
-            const uint64_t b = i0 + combine_group_begin(gi, R), e = i0 + combine_group_end(gi, R, k);
-            if (gok[gi]) { memset(ok + b, 1, e - b); continue; }
-            t_combine.failed++; t_combine.rechecked += e - b;
-            CHK(multi_checks(ks, s, g->d_gen, qn, c + b, pi + b, xs + b, ys + b * n, n, np, e - b, ok + b));
-        }
-    }
-    return KZG_HIP_OK;
+            return combine_group_checks(s, g->d_gen, qn, d_a.p, d_b.p, G, gok);
+        },
+        [&](uint64_t b, uint64_t e) { return multi_checks(ks, s, g->d_gen, qn, c + b, pi + b, xs + b, ys + b * n, n, np, e - b, ok + b); });
     KZG_CATCH
 }
 
@@ -568,31 +544,16 @@ int kzg_hip_check_proof_single_batch_combined(kzg_hip_kzg *ks, const void *commi
     if (!combine_route(count)) return kzg_checks(s, g->d_gen, g->d_s, commitments_g1, proofs_g1, ys_fr, nullptr, xs_fr, nullptr, count, ok);
     t_combine.route = 1;
     const combine_seed seed = combine_seed_of(seed32);
-    const uint64_t R = combine_rows(), chunk = combine_chunk_groups(R) * R;
+    const uint64_t R = combine_rows();
     const g1j *c = (const g1j *)commitments_g1, *pi = (const g1j *)proofs_g1; const fr *xs = (const fr *)xs_fr, *ys = (const fr *)ys_fr;
-    std::vector<uint8_t> gok;
-    for (uint64_t i0 = 0; i0 < count; i0 += chunk) {
-        const uint64_t k = count - i0 < chunk ? count - i0 : chunk, G = combine_group_count(k, R);
-        {
-            dtmp<g1j> d_c(s), d_pi(s), d_a(s), d_b(s); dtmp<fr> d_x(s), d_y(s);
-            CHK(d_c.alloc(k)); CHK(d_pi.alloc(k)); CHK(d_x.alloc(k)); CHK(d_y.alloc(k)); CHK(d_a.alloc(G)); CHK(d_b.alloc(G));
-            HIPCHK(hipMemcpyAsync(d_c.p, c + i0, k * sizeof(g1j), hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(d_pi.p, pi + i0, k * sizeof(g1j), hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(d_x.p, xs + i0, k * sizeof(fr), hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(d_y.p, ys + i0, k * sizeof(fr), hipMemcpyHostToDevice, s));
-            CHK(combine_group_sums(s, seed, d_c.p, d_pi.p, true, d_x.p, d_y.p, nullptr, i0, k, R, d_a.p, d_b.p, false));
-            gok.assign(G, 0);
-            CHK(combine_group_checks(s, g->d_gen, g->d_s, d_a.p, d_b.p, G, gok.data()));
-        }
-        t_combine.groups += G;
-        for (uint64_t gi = 0; gi < G; gi++) {
-            const uint64_t b = i0 + combine_group_begin(gi, R), e = i0 + combine_group_end(gi, R, k);
-            if (gok[gi]) { memset(ok + b, 1, e - b); continue; }
-            t_combine.failed++; t_combine.rechecked += e - b;
-            CHK(kzg_checks(s, g->d_gen, g->d_s, c + b, pi + b, ys + b, nullptr, xs + b, nullptr, e - b, ok + b));
-        }
-    }
-    return KZG_HIP_OK;
+    return combine_drive(count, R, combine_chunk_groups(R) * R, ok, t_combine,
+        [&](uint64_t i0, uint64_t k, uint64_t G, uint8_t *, uint8_t *gok) -> int {
+            dtmp<g1j> d_a(s), d_b(s);
+            CHK(d_a.alloc(G)); CHK(d_b.alloc(G));
+            CHK(combine_single_chunk(s, seed, c + i0, pi + i0, xs + i0, ys + i0, i0, k, R, d_a.p, d_b.p, false));
+            return combine_group_checks(s, g->d_gen, g->d_s, d_a.p, d_b.p, G, gok);
+        },
+        [&](uint64_t b, uint64_t e) { return kzg_checks(s, g->d_gen, g->d_s, c + b, pi + b, ys + b, nullptr, xs + b, nullptr, e - b, ok + b); });
     KZG_CATCH
 }
 
@@ -611,38 +572,23 @@ int kzg_hip_eth_verify_kzg_proof_batch_combined(kzg_hip_eth *eth, const void *co
     if (!combine_route(count)) return eth_checks(s, g->d_gen, g->d_s, commitments48, zs_le32, ys_le32, proofs48, count, result);
     t_combine.route = 1;
     const combine_seed seed = combine_seed_of(seed32);
-    const uint64_t R = combine_rows(), chunk = combine_chunk_groups(R) * R;
+    const uint64_t R = combine_rows();
     const uint8_t *c48 = (const uint8_t *)commitments48, *pi48 = (const uint8_t *)proofs48, *zs = (const uint8_t *)zs_le32, *ys = (const uint8_t *)ys_le32;
-    std::vector<uint8_t> gok, st;
-    for (uint64_t i0 = 0; i0 < count; i0 += chunk) {
-        const uint64_t k = count - i0 < chunk ? count - i0 : chunk, G = combine_group_count(k, R);
-        {
+    return combine_drive(count, R, combine_chunk_groups(R) * R, result, t_combine,
+        [&](uint64_t i0, uint64_t k, uint64_t G, uint8_t *status, uint8_t *gok) -> int {
             dtmp<uint8_t> d_c48(s), d_pi48(s), d_z32(s), d_y32(s), d_cbad(s), d_pbad(s), d_st(s); dtmp<g1j> d_c(s), d_pi(s), d_a(s), d_b(s); dtmp<fr> d_z(s), d_y(s);
-            CHK(d_c48.alloc(48 * k)); CHK(d_pi48.alloc(48 * k)); CHK(d_z32.alloc(32 * k)); CHK(d_y32.alloc(32 * k)); CHK(d_cbad.alloc(k)); CHK(d_pbad.alloc(k));
+            CHK(upload(d_c48, c48 + 48 * i0, 48 * k)); CHK(upload(d_pi48, pi48 + 48 * i0, 48 * k)); CHK(upload(d_z32, zs + 32 * i0, 32 * k));
+            CHK(upload(d_y32, ys + 32 * i0, 32 * k)); CHK(d_cbad.alloc(k)); CHK(d_pbad.alloc(k));
             CHK(d_st.alloc(k)); CHK(d_c.alloc(k)); CHK(d_pi.alloc(k)); CHK(d_z.alloc(k)); CHK(d_y.alloc(k)); CHK(d_a.alloc(G)); CHK(d_b.alloc(G));
-            HIPCHK(hipMemcpyAsync(d_c48.p, c48 + 48 * i0, 48 * k, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(d_pi48.p, pi48 + 48 * i0, 48 * k, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(d_z32.p, zs + 32 * i0, 32 * k, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(d_y32.p, ys + 32 * i0, 32 * k, hipMemcpyHostToDevice, s));
             launch_g1_decompress_rows(s, d_c48.p, d_c.p, k, d_cbad.p, false);
             launch_g1_decompress_rows(s, d_pi48.p, d_pi.p, k, d_pbad.p, false);
             launch_eth_combine_fields(s, d_z32.p, d_y32.p, d_cbad.p, d_pbad.p, k, d_z.p, d_y.p, d_st.p);
             CHK(combine_group_sums(s, seed, d_c.p, d_pi.p, false, d_z.p, d_y.p, d_st.p, i0, k, R, d_a.p, d_b.p, false));
-            drain_on_exit drain(s);                                                              // (an error below leaves no copy into st in flight)
-            st.assign(k, 0); gok.assign(G, 0);
-            HIPCHK(hipMemcpyAsync(st.data(), d_st.p, k, hipMemcpyDeviceToHost, s));
-            CHK(combine_group_checks(s, g->d_gen, g->d_s, d_a.p, d_b.p, G, gok.data()));
-        }
-        memcpy(result + i0, st.data(), k);                                                       // the statuses first: 0 where the row's inputs are valid
-        t_combine.groups += G;
-        for (uint64_t gi = 0; gi < G; gi++) {
-            const uint64_t b = i0 + combine_group_begin(gi, R), e = i0 + combine_group_end(gi, R, k);
-            if (gok[gi]) { for (uint64_t i = b; i < e; i++) if (!result[i]) result[i] = 1; continue; }
-            t_combine.failed++; t_combine.rechecked += e - b;
-            CHK(eth_checks(s, g->d_gen, g->d_s, c48 + 48 * b, zs + 32 * b, ys + 32 * b, pi48 + 48 * b, e - b, result + b));
-        }
-    }
-    return KZG_HIP_OK;
+            drain_on_exit drain(s);                                                              // (an error below leaves no copy into status in flight)
+            HIPCHK(hipMemcpyAsync(status, d_st.p, k, hipMemcpyDeviceToHost, s));                 // 0 where the row's inputs are valid
+            return combine_group_checks(s, g->d_gen, g->d_s, d_a.p, d_b.p, G, gok);
+        },
+        [&](uint64_t b, uint64_t e) { return eth_checks(s, g->d_gen, g->d_s, c48 + 48 * b, zs + 32 * b, ys + 32 * b, pi48 + 48 * b, e - b, result + b); });
     KZG_CATCH
 }
 
@@ -657,13 +603,9 @@ int kzg_hip_test_combine_points(kzg_hip_kzg *ks, const void *commitments_g1, con
     const combine_seed seed = combine_seed_of(seed32);
     const uint64_t R = combine_rows(), G = combine_group_count(count, R);
     if (G > COMBINE_CHUNK_GROUPS || G > combine_chunk_groups(R)) return KZG_HIP_ERR_TOO_WIDE;
-    dtmp<g1j> d_c(s), d_pi(s), d_a(s), d_b(s); dtmp<fr> d_x(s), d_y(s);
-    CHK(d_c.alloc(count)); CHK(d_pi.alloc(count)); CHK(d_x.alloc(count)); CHK(d_y.alloc(count)); CHK(d_a.alloc(G)); CHK(d_b.alloc(G));
-    HIPCHK(hipMemcpyAsync(d_c.p, commitments_g1, count * sizeof(g1j), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_pi.p, proofs_g1, count * sizeof(g1j), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_x.p, xs_fr, count * sizeof(fr), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_y.p, ys_fr, count * sizeof(fr), hipMemcpyHostToDevice, s));
-    CHK(combine_group_sums(s, seed, d_c.p, d_pi.p, true, d_x.p, d_y.p, nullptr, 0, count, R, d_a.p, d_b.p, true));
+    dtmp<g1j> d_a(s), d_b(s);
+    CHK(d_a.alloc(G)); CHK(d_b.alloc(G));
+    CHK(combine_single_chunk(s, seed, (const g1j *)commitments_g1, (const g1j *)proofs_g1, (const fr *)xs_fr, (const fr *)ys_fr, 0, count, R, d_a.p, d_b.p, true));
     HIPCHK(hipMemcpyAsync(out_a_g1, d_a.p, G * sizeof(g1j), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(out_b_g1, d_b.p, G * sizeof(g1j), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -758,14 +700,12 @@ int kzg_hip_eth_verify_aggregate_kzg_proof_batch(kzg_hip_eth *eth, const void *b
         dtmp<uint64_t> d_off(s); dtmp<fr> d_r(s), d_z(s), d_y(s), d_agg(s), d_q(s), d_pow(s); dtmp<uint32_t> d_flag(s);
         dtmp<g1j> d_cpts(s), d_cmul(s), d_sum(s), d_sumk(s), d_pik(s), d_p0(s), d_p1(s);
         const uint64_t extra = eth_quotient_scratch_elems(n, S);
-        CHK(d_blobs.alloc(B * n * 32)); CHK(d_comm.alloc(B * 48)); CHK(d_pi48.alloc(S * 48)); CHK(d_cbad.alloc(B)); CHK(d_pbad.alloc(S)); CHK(d_st.alloc(S));
-        CHK(d_ok.alloc(S)); CHK(d_off.alloc(S + 1)); CHK(d_r.alloc(S)); CHK(d_z.alloc(S)); CHK(d_y.alloc(S)); CHK(d_agg.alloc(S * n)); CHK(d_q.alloc(S * n + extra));
+        CHK(d_blobs.alloc(B * n * 32)); CHK(d_comm.alloc(B * 48)); CHK(upload(d_pi48, proofs + 48 * j0, S * 48)); CHK(d_cbad.alloc(B)); CHK(d_pbad.alloc(S)); CHK(d_st.alloc(S));
+        CHK(d_ok.alloc(S)); CHK(upload(d_off, off.data(), S + 1)); CHK(d_r.alloc(S)); CHK(d_z.alloc(S)); CHK(d_y.alloc(S)); CHK(d_agg.alloc(S * n)); CHK(d_q.alloc(S * n + extra));
         CHK(d_pow.alloc(B)); CHK(d_flag.alloc(S)); CHK(d_cpts.alloc(B)); CHK(d_cmul.alloc(B)); CHK(d_sum.alloc(S)); CHK(d_sumk.alloc(S)); CHK(d_pik.alloc(S));
         CHK(d_p0.alloc(S)); CHK(d_p1.alloc(S));
         HIPCHK(hipMemsetAsync(d_st.p, 0, S, s));
         HIPCHK(hipMemsetAsync(d_flag.p, 0, S * 4, s));
-        HIPCHK(hipMemcpyAsync(d_off.p, off.data(), (S + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_pi48.p, proofs + 48 * j0, S * 48, hipMemcpyHostToDevice, s));
         if (B) {
             HIPCHK(hipMemcpyAsync(d_comm.p, c_comms, B * 48, hipMemcpyHostToDevice, s));
             CHK(h2d_copy(d_blobs.p, c_blobs, B * n * 32, s));
@@ -837,10 +777,8 @@ int kzg_hip_test_sha256_lanes(kzg_hip_fft *fs, const void *data, const uint64_t 
     stream_lease lease(fs);
     hipStream_t s = lease.s;
     dtmp<uint8_t> d_data(s); dtmp<uint64_t> d_off(s), d_len(s); dtmp<uint32_t> d_out(s);
-    CHK(d_data.alloc(bytes)); CHK(d_off.alloc(rows)); CHK(d_len.alloc(rows)); CHK(d_out.alloc(8 * rows));
+    CHK(d_data.alloc(bytes)); CHK(upload(d_off, offsets, rows)); CHK(upload(d_len, lens, rows)); CHK(d_out.alloc(8 * rows));
     if (bytes) HIPCHK(hipMemcpyAsync(d_data.p, data, bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_off.p, offsets, rows * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_len.p, lens, rows * 8, hipMemcpyHostToDevice, s));
     launch_test_sha256_lanes(s, d_data.p, d_off.p, d_len.p, rows, d_out.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out32, d_out.p, 32 * rows, hipMemcpyDeviceToHost, s));
@@ -855,8 +793,7 @@ int kzg_hip_test_hash_to_bls_field_lanes(kzg_hip_fft *fs, const void *digests32,
     stream_lease lease(fs);
     hipStream_t s = lease.s;
     dtmp<uint8_t> d_in(s); dtmp<fr> d_out(s);
-    CHK(d_in.alloc(32 * rows)); CHK(d_out.alloc(rows));
-    HIPCHK(hipMemcpyAsync(d_in.p, digests32, 32 * rows, hipMemcpyHostToDevice, s));
+    CHK(upload(d_in, digests32, 32 * rows)); CHK(d_out.alloc(rows));
     launch_test_hash_to_bls_field_lanes(s, d_in.p, rows, d_out.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_fr, d_out.p, rows * sizeof(fr), hipMemcpyDeviceToHost, s));
@@ -873,12 +810,10 @@ static int pairing_test(kzg_hip_fft *fs, const void *g1, const void *g2, uint64_
     stream_lease lease(fs);
     hipStream_t s = lease.s;
     dtmp<g1j> d_p(s); dtmp<g2j> d_q(s); dtmp<fp> d_out(s);
-    CHK(d_p.alloc(n)); CHK(d_q.alloc(n)); CHK(d_out.alloc(12 * n));
+    CHK(upload(d_p, g1, n)); CHK(upload(d_q, g2, n)); CHK(d_out.alloc(12 * n));
     g2_prepared *d_lines = nullptr;
     HIPCHK(hipMalloc((void **)&d_lines, n * sizeof(g2_prepared)));
     std::unique_ptr<g2_prepared, hipError_t (*)(void *)> own(d_lines, hipFree);
-    HIPCHK(hipMemcpyAsync(d_p.p, g1, n * sizeof(g1j), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_q.p, g2, n * sizeof(g2j), hipMemcpyHostToDevice, s));
     launch_g2_prepare(s, d_q.p, n, d_lines);
     if (wave) launch_pairing_value_wave(s, d_p.p, d_lines, n, d_out.p);
     else launch_pairing_value(s, d_p.p, d_lines, n, d_out.p);
@@ -899,9 +834,7 @@ int kzg_hip_test_wave_fp12_op(kzg_hip_fft *fs, int op, const void *a, const void
     stream_lease lease(fs);
     hipStream_t s = lease.s;
     dtmp<fp> d_a(s), d_b(s), d_out(s);
-    CHK(d_a.alloc(12 * n)); CHK(d_b.alloc(12 * n)); CHK(d_out.alloc(12 * n));
-    HIPCHK(hipMemcpyAsync(d_a.p, a, 12 * n * sizeof(fp), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_b.p, b, 12 * n * sizeof(fp), hipMemcpyHostToDevice, s));
+    CHK(upload(d_a, a, 12 * n)); CHK(upload(d_b, b, 12 * n)); CHK(d_out.alloc(12 * n));
     launch_wave_fp12_op(s, op, d_a.p, d_b.p, n, d_out.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out.p, 12 * n * sizeof(fp), hipMemcpyDeviceToHost, s));

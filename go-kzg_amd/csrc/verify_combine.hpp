@@ -1,5 +1,6 @@
 // verify_combine.hpp -- what one lane of the combination kernels (k_verify_combine.hip) computes, as host/device functions: the weights of a
-// random linear combination of KZG checks, the term scalars of a group's two MSMs, and the layout of a group's terms.
+// random linear combination of KZG checks, the term scalars of a group's two MSMs, and the layout of a group's terms.  Below them, as a plain host
+// template, the loop that every _combined entry runs over a call's chunks and groups (combine_drive).
 //
 // For a group g of consecutive rows i with 128-bit weights r_i
 //     A_g = sum r_i pi_i,     B_g = sum r_i C_i + sum (r_i x_i) pi_i - (sum r_i y_i) G1,
@@ -10,6 +11,7 @@
 #pragma once
 #include "verify_inputs.hpp"
 #include "sha256_lane.hpp"
+#include <vector>
 
 namespace kzg {
 
@@ -61,6 +63,35 @@ KZG_HD uint64_t combine_group_count(uint64_t count, uint64_t R) { return (count 
 KZG_HD uint64_t combine_group_begin(uint64_t g, uint64_t R) { return g * R; }
 KZG_HD uint64_t combine_group_end(uint64_t g, uint64_t R, uint64_t count) { return (g + 1) * R < count ? (g + 1) * R : count; }
 KZG_HD uint64_t combine_term_stride(uint64_t R) { return 2 * R + 1; }
+
+// what a _combined call did: route 1 when it combined, the group checks it ran, those that failed, and the rows re-checked one by one
+struct combine_stats { uint64_t route, groups, failed, rechecked; };
+
+// The host loop of every _combined entry (capi_verify.hip), free of the device: `count` rows in chunks of chunk_rows (a multiple of R, so that a
+// chunk holds whole groups of the call), one group check per R rows, the rows of a failing group checked again one by one.
+//   chunk(i0, k, G, status, gok) -> code: everything rows i0 .. i0 + k do on the device.  It fills gok[G] (1: the group passed) and may give
+//       a row a status other than 0 (status[k], zeroed: the eth form's 2 / 3); it hashes a row's weight from i0 + the row's index in the chunk,
+//       its index in the CALL, and returns with nothing in flight into either buffer.
+//   recheck(b, e) -> code: writes out[b .. e) itself.
+// out is written only after a chunk's code is 0: a row of a passing group gets its status, or 1 where that is 0; a failing group is left to
+// recheck alone.  The first code other than 0 from either is returned at once and nothing is called after it.
+template <class Chunk, class Recheck>
+int combine_drive(uint64_t count, uint64_t R, uint64_t chunk_rows, uint8_t *out, combine_stats &st, Chunk chunk, Recheck recheck) {
+    std::vector<uint8_t> status, gok;
+    for (uint64_t i0 = 0; i0 < count; i0 += chunk_rows) {
+        const uint64_t k = count - i0 < chunk_rows ? count - i0 : chunk_rows, G = combine_group_count(k, R);
+        status.assign(k, 0); gok.assign(G, 0);
+        if (const int code = chunk(i0, k, G, status.data(), gok.data())) return code;
+        st.groups += G;
+        for (uint64_t g = 0; g < G; g++) {
+            const uint64_t b = combine_group_begin(g, R), e = combine_group_end(g, R, k);
+            if (gok[g]) { for (uint64_t i = b; i < e; i++) out[i0 + i] = status[i] ? status[i] : 1; continue; }
+            st.failed++; st.rechecked += e - b;
+            if (const int code = recheck(i0 + b, i0 + e)) return code;
+        }
+    }
+    return 0;
+}
 
 // eth.VerifyKZGProof's field parsing (eth/eth.go:114-135) in front of the combination: z and y as Montgomery images, and the row's status from
 // them and from the decompression flags of its commitment and proof, in the reference's order (z, y, commitment, proof): 0 valid, 2, 3

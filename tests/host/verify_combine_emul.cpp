@@ -1,6 +1,7 @@
 // Host build of verify_combine.hpp for tests/test_verify_combine_host.py: the lane bodies of k_verify_combine.hip on the CPU -- the weights, a
 // row's term scalars, and a whole group pass the way k_combine_scalars runs it (the partition into groups, the layout of a group's slice, the
-// sum over a group and the generator's scalar).  Scalars cross the boundary as 32 little-endian bytes in STANDARD form.
+// sum over a group and the generator's scalar), and the host loop of the _combined entries (combine_drive) over a model of the device.  Scalars
+// cross the boundary as 32 little-endian bytes in STANDARD form.
 #include "verify_combine.hpp"
 
 using namespace kzg;
@@ -58,5 +59,37 @@ void vc_eth_fields(const uint8_t *zs32, const uint8_t *ys32, const uint8_t *c_ba
         fr_to_le(from_mont<FrP>(z), z_out32 + 32 * t);
         fr_to_le(from_mont<FrP>(y), y_out32 + 32 * t);
     }
+}
+// combine_drive over a CPU model of the device.  want[i] in {0, 1, 2, 3} is the byte row i has to end with: the model's chunk gives the 2 / 3
+// rows their status and passes a group iff none of its rows wants 0, its recheck writes want[b .. e).  Both log their arguments -- (i0, k, G)
+// per chunk, (b, e) per re-check -- and calls[0 .. 1] count them.  Call number fail_chunk / fail_recheck of its kind (from 0; -1: none) logs
+// and returns `code` without writing; a chunk whose buffers do not arrive zeroed returns 99.  stats = groups, failed, rechecked.
+int vc_drive(const uint8_t *want, uint64_t count, uint64_t R, uint64_t chunk_rows, int64_t fail_chunk, int64_t fail_recheck, int code, uint8_t *out, uint64_t *chunk_log,
+             uint64_t *recheck_log, uint64_t *calls, uint64_t *stats) {
+    combine_stats st{};
+    calls[0] = calls[1] = 0;
+    const int got = combine_drive(count, R, chunk_rows, out, st,
+        [&](uint64_t i0, uint64_t k, uint64_t G, uint8_t *status, uint8_t *gok) -> int {
+            uint64_t *log = chunk_log + 3 * calls[0];
+            log[0] = i0; log[1] = k; log[2] = G;
+            if ((int64_t)calls[0]++ == fail_chunk) return code;
+            for (uint64_t t = 0; t < k; t++) if (status[t]) return 99;
+            for (uint64_t g = 0; g < G; g++) if (gok[g]) return 99;
+            for (uint64_t t = 0; t < k; t++) if (want[i0 + t] > 1) status[t] = want[i0 + t];
+            for (uint64_t g = 0; g < G; g++) {
+                gok[g] = 1;
+                for (uint64_t t = combine_group_begin(g, R); t < combine_group_end(g, R, k); t++) if (!want[i0 + t]) gok[g] = 0;
+            }
+            return 0;
+        },
+        [&](uint64_t b, uint64_t e) -> int {
+            uint64_t *log = recheck_log + 2 * calls[1];
+            log[0] = b; log[1] = e;
+            if ((int64_t)calls[1]++ == fail_recheck) return code;
+            for (uint64_t i = b; i < e; i++) out[i] = want[i];
+            return 0;
+        });
+    stats[0] = st.groups; stats[1] = st.failed; stats[2] = st.rechecked;
+    return got;
 }
 }

@@ -1,7 +1,8 @@
 """Batches of KZG proofs checked by random linear combination per group of rows (kzg_hip_check_proof_single_batch_combined,
 kzg_hip_eth_verify_kzg_proof_batch_combined; k_verify_combine.hip): the mask is the per-row entry's on the crafted rows of tests/verify_cases.py,
 errors that cancel under equal weights are caught, only a failing group is re-checked, sums that double or vanish pass, A_g and B_g are the
-points Python computes, and the routing switches do what README says.  Group size and route are set through the per-call switches."""
+points Python computes, and the routing switches do what README says, and a call that spans two chunks gives the per-row entry's output.  Group size and route are set
+through the per-call switches."""
 import ctypes as C
 import hashlib
 import json
@@ -344,3 +345,41 @@ def test_routing_and_error_codes(kz, ks16, crafted, monkeypatch):
         codes.append(e.value.status)
     assert codes == [kz.ERR_BAD_ARG, kz.ERR_BAD_ARG]
     ks.close(); fs.close()
+
+
+# ---------------- 10. across a chunk boundary ----------------
+# a chunk holds at most 1 024 groups: at five rows per group 5 127 rows split after 5 120, into 1 024 groups and 2 (of five and two rows)
+CROSS, CROSS_BAD = 5127, (5119, 5120, 5126)      # the last row of the first chunk, the first of the second, the last of the call
+
+
+def test_chunk_boundary_single(kz, ks16, crafted, monkeypatch):
+    route(monkeypatch, "always", 5)
+    valid = [i for i, w in enumerate(crafted.want) if w]
+    idx = [valid[k % len(valid)] for k in range(CROSS)]
+    for at in CROSS_BAD:
+        idx[at] = [r[0] for r in crafted.rows].index("ordinary/y+1_1")
+    sub = crafted.take(idx)
+    got = ks16.check_proof_single_batch_combined(*sub.arrays(), seed=SEED)
+    st = kz.combine_stats()
+    assert np.array_equal(got, ks16.check_proof_single_batch(*sub.arrays())) and list(np.nonzero(~got)[0]) == list(CROSS_BAD)
+    assert (st["route"], st["rows"], st["groups"], st["failed"], st["rechecked"]) == ("combined", 5, 1026, 3, 5 + 5 + 2), st
+
+
+def test_chunk_boundary_eth(kz, eth, monkeypatch):
+    """a status-2 and a status-3 row in groups of the first chunk that are otherwise valid, and a status-3 row beyond row 5 120, where both
+    groups hold an invalid row: the status rows cause no re-check"""
+    route(monkeypatch, "always", 5)
+    rows = {r[0]: r for r in vi.eth_rows(1337, random.Random(4))}
+    valid = [r for r in rows.values() if r[5] == 1]
+    batch = [valid[k % len(valid)] for k in range(CROSS)]
+    for at in CROSS_BAD:
+        batch[at] = rows["ordinary/y+1_0"]
+    batch[7] = batch[5122] = rows["bytes/commitment_outside_g1"]
+    batch[5112] = rows["bytes/z=2^256-1"]
+    arrays = vi.eth_arrays(batch)
+    got = eth.verify_kzg_proof_batch_combined(*arrays, seed=SEED)
+    st = kz.combine_stats()
+    want = [r[5] for r in batch]
+    assert (want[7], want[5112], want[5122]) == (3, 2, 3) and [i for i, w in enumerate(want) if w == 0] == list(CROSS_BAD)
+    assert list(got) == want and list(got) == list(eth.verify_kzg_proof_batch(*arrays))
+    assert (st["route"], st["rows"], st["groups"], st["failed"], st["rechecked"]) == ("combined", 5, 1026, 3, 5 + 5 + 2), st

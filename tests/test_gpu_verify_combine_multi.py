@@ -1,7 +1,8 @@
 """Batches of KZG multi-proofs checked by random linear combination per group of rows (kzg_hip_check_proof_multi_batch_combined;
 k_verify_combine_multi.hip): the mask is the per-row entry's on the crafted rows of tests/verify_cases.py, errors that cancel under equal weights
 are caught, only a failing group is re-checked, group and tile edges, J_g / A_g / B_g are what Python computes, the proofs of DAUsingFK20Multi
-pass in whole groups, no commitment table is built, and routing and status codes are the per-row entry's.  Rows are scalars: C = [c] G1,
+pass in whole groups, no commitment table is built, routing and status codes are the per-row entry's, and a call that spans two chunks gives
+the per-row entry's output.  Rows are scalars: C = [c] G1,
 pi = [t] G1 with the setup's secret known, so truth is modular arithmetic."""
 import ctypes as C
 import hashlib
@@ -420,3 +421,20 @@ def test_eight_threads_on_one_handle(kz, ks16, crafted, monkeypatch):
     serial = {k: mask(ks16.check_proof_multi_batch_combined(*subs[k].arrays(), seed=SEED)) for k in (0, 1)}
     assert serial[0] == subs[0].want and serial[1] == subs[1].want
     assert out == [serial[k % 2] for k in range(8)]
+
+
+# ---------------- 10. across a chunk boundary ----------------
+def test_chunk_boundary(kz, ks16, pools, monkeypatch):
+    """a chunk holds at most 1 024 groups: at five rows per group 5 127 rows split after 5 120, into 1 024 groups and 2 (of five and two rows).
+    One invalid row on the last row of the first chunk, the first of the second and the last of the call; the pool with the fewest values"""
+    route(monkeypatch, "always", 5)
+    bad = (5119, 5120, 5126)
+    sub = pools[0][min(pools[0])].take([i % POOL for i in range(5127)])
+    cs = sub.cs.copy()
+    for at in bad:
+        cs[at] = pools[1]
+    got = ks16.check_proof_multi_batch_combined(cs, sub.pis, sub.xs, sub.ys, seed=SEED)
+    st = kz.combine_stats()
+    assert np.array_equal(got, ks16.check_proof_multi_batch(cs, sub.pis, sub.xs, sub.ys)) and list(np.nonzero(~got)[0]) == list(bad)
+    expect_stats(kz, [i not in bad for i in range(5127)], 5)
+    assert (st["groups"], st["failed"], st["rechecked"]) == (1026, 3, 5 + 5 + 2), st

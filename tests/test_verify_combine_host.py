@@ -1,6 +1,7 @@
 """The lane bodies of the combined proof checks (go-kzg_amd/csrc/verify_combine.hpp) compiled for the host (tests/host/verify_combine_emul.cpp):
-the weights against hashlib, a group's term scalars and the generator's scalar against Python integers, the partition into groups, and the zero
-weight of a malformed row.  CPU only."""
+the weights against hashlib, a group's term scalars and the generator's scalar against Python integers, the partition into groups, the zero
+weight of a malformed row, and the host loop of the _combined entries (combine_drive) over a model of the device: chunks, marks, re-checks,
+counters and error returns across chunk boundaries.  CPU only."""
 import ctypes as C
 import hashlib
 import os
@@ -40,6 +41,8 @@ def emul():
     lib.vc_partition.argtypes = [u64, u64, C.POINTER(u64)]
     lib.vc_partition.restype = u64
     lib.vc_eth_fields.argtypes = [C.c_char_p] * 4 + [u64] + [C.c_char_p] * 3
+    lib.vc_drive.argtypes = [C.c_char_p, u64, u64, u64, C.c_int64, C.c_int64, C.c_int, C.c_char_p] + [C.POINTER(u64)] * 4
+    lib.vc_drive.restype = C.c_int
     return lib
 
 
@@ -137,3 +140,109 @@ def test_eth_fields_status_order(emul):
     emul.vc_eth_fields(le([r[0] for r in rows]), le([r[1] for r in rows]), bytes(r[2] for r in rows), bytes(r[3] for r in rows), n, zo, yo, st)
     assert list(st.raw) == [r[4] for r in rows]
     assert ints(zo, n) == [r[0] if not r[4] else 0 for r in rows] and ints(yo, n) == [r[1] if not r[4] else 0 for r in rows]
+
+
+# ---------------- the host loop of the _combined entries ----------------
+FILL = 0xEE      # what `out` holds before a call: a byte no route writes
+
+
+def drive(emul, want, rows, chunk_rows, fail_chunk=-1, fail_recheck=-1, code=0):
+    """combine_drive over the model: (code, out, [(i0, k, G)], [(b, e)], (groups, failed, rechecked))"""
+    count = len(want)
+    out = C.create_string_buffer(bytes([FILL]) * count, count)
+    chunk_log, recheck_log = (C.c_uint64 * (3 * (count // chunk_rows + 1)))(), (C.c_uint64 * (2 * count))()
+    calls, stats = (C.c_uint64 * 2)(), (C.c_uint64 * 3)()
+    got = emul.vc_drive(bytes(want), count, rows, chunk_rows, fail_chunk, fail_recheck, code, out, chunk_log, recheck_log, calls, stats)
+    return (got, list(out.raw), [tuple(chunk_log[3 * t:3 * t + 3]) for t in range(calls[0])], [tuple(recheck_log[2 * t:2 * t + 2]) for t in range(calls[1])],
+            tuple(stats))
+
+
+def want_drive(want, rows, chunk_rows):
+    """the chunks (i0, k, G) of a call and its groups (b, e) chunk by chunk: a group never spans two chunks"""
+    count = len(want)
+    chunks = [(i0, min(chunk_rows, count - i0), -(-min(chunk_rows, count - i0) // rows)) for i0 in range(0, count, chunk_rows)]
+    groups = [[(i0 + g * rows, min(i0 + k, i0 + (g + 1) * rows)) for g in range(G)] for i0, k, G in chunks]
+    return chunks, groups
+
+
+def drive_counts(rows, chunk_rows):
+    return sorted({c for c in (1, rows - 1, rows, rows + 1, chunk_rows, chunk_rows + 1, 2 * chunk_rows + rows + 1) if c > 0})
+
+
+@pytest.mark.parametrize("statuses", [False, True])
+@pytest.mark.parametrize("chunk_groups", [1, 3])
+@pytest.mark.parametrize("rows", [1, 5])
+def test_drive_marks_and_rechecks_across_chunks(emul, rows, chunk_groups, statuses):
+    """an invalid row on the last row of a chunk, the first row of the next and the last row of the call, each alone and all at once, and no
+    invalid row at all: the output, the chunks, the re-checked ranges and the counters"""
+    chunk_rows = chunk_groups * rows
+    for count in drive_counts(rows, chunk_rows):
+        places = sorted({i for i in (chunk_rows - 1, chunk_rows, count - 1) if i < count})
+        for invalid in [[]] + [[i] for i in places] + [places]:
+            want = [1] * count
+            if statuses:
+                for i in range(1, count, 3):
+                    want[i] = 2 + i // 3 % 2
+            for i in invalid:
+                want[i] = 0
+            code, out, chunks, rechecks, stats = drive(emul, want, rows, chunk_rows)
+            where = (count, invalid)
+            assert code == 0 and out == want, where
+            want_chunks, groups = want_drive(want, rows, chunk_rows)
+            assert chunks == want_chunks and all(i0 % chunk_rows == 0 for i0, _, _ in chunks), where
+            assert [i0 for i0, _, _ in chunks] == [sum(k for _, k, _ in chunks[:t]) for t in range(len(chunks))] and sum(k for _, k, _ in chunks) == count, where
+            failing = [(b, e) for chunk in groups for b, e in chunk if 0 in want[b:e]]
+            assert rechecks == failing and len(failing) == len({i // rows for i in invalid}), where
+            assert stats == (sum(G for _, _, G in chunks), len(failing), sum(e - b for b, e in failing)), where
+            assert stats[0] == sum(-(-k // rows) for _, k, _ in chunks), where
+
+
+def test_drive_group_of_status_rows_only(emul):
+    """a group whose rows all carry a status passes (no live row speaks against it), is not re-checked and keeps its bytes; at one row per group too"""
+    want = [1] * 5 + [2, 3, 3, 2, 3] + [1, 1, 0, 1, 1] + [3, 2, 2, 2, 3] + [1]
+    code, out, chunks, rechecks, stats = drive(emul, want, 5, 15)
+    assert code == 0 and out == want
+    assert chunks == [(0, 15, 3), (15, 6, 2)] and rechecks == [(10, 15)] and stats == (5, 1, 5)
+    want = [1, 2, 0, 3, 1]
+    code, out, chunks, rechecks, stats = drive(emul, want, 1, 3)
+    assert code == 0 and out == want
+    assert chunks == [(0, 3, 3), (3, 2, 2)] and rechecks == [(2, 3)] and stats == (5, 1, 1)
+
+
+@pytest.mark.parametrize("chunk_groups", [1, 3])
+@pytest.mark.parametrize("rows", [1, 5])
+def test_drive_returns_a_chunk_error_at_once(emul, rows, chunk_groups):
+    """the second chunk fails: its code comes back unchanged, nothing is called after it, and neither its rows nor later ones are written"""
+    chunk_rows = chunk_groups * rows
+    count = 2 * chunk_rows + rows + 1
+    want = [1] * count
+    want[chunk_rows - 1] = want[chunk_rows] = want[count - 1] = 0
+    if chunk_rows > 1:
+        want[0] = 3
+    for err in (8, 1):
+        code, out, chunks, rechecks, stats = drive(emul, want, rows, chunk_rows, fail_chunk=1, code=err)
+        assert code == err
+        assert chunks == [(0, chunk_rows, chunk_groups), (chunk_rows, chunk_rows, chunk_groups)]
+        assert rechecks == [(chunk_rows - rows, chunk_rows)]
+        assert out == want[:chunk_rows] + [FILL] * (count - chunk_rows)
+        assert stats == (chunk_groups, 1, rows)
+
+
+@pytest.mark.parametrize("chunk_groups", [1, 3])
+@pytest.mark.parametrize("rows", [1, 5])
+def test_drive_returns_a_recheck_error_at_once(emul, rows, chunk_groups):
+    """the re-check of the second chunk's first group fails, then (three groups per chunk) that of its second group: the code comes back
+    unchanged, nothing is called after it, and no row from the failing group on is written"""
+    chunk_rows = chunk_groups * rows
+    count = 2 * chunk_rows + rows + 1
+    for at in sorted({chunk_rows, chunk_rows + (chunk_groups - 1) // 2 * rows}):      # the first row of the group whose re-check fails
+        want = [1] * count
+        want[chunk_rows - 1] = want[at] = want[count - 1] = 0
+        if chunk_rows > 1:
+            want[0] = 2
+        code, out, chunks, rechecks, stats = drive(emul, want, rows, chunk_rows, fail_recheck=1, code=8)
+        assert code == 8
+        assert chunks == [(0, chunk_rows, chunk_groups), (chunk_rows, chunk_rows, chunk_groups)]
+        assert rechecks == [(chunk_rows - rows, chunk_rows), (at, at + rows)]
+        assert out == want[:at] + [FILL] * (count - at)
+        assert stats == (2 * chunk_groups, 2, 2 * rows)                              # counted before the call, as the entries always have
