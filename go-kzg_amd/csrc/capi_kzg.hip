@@ -89,11 +89,13 @@ static double fb_handle_budget_gb(kzg_hip_kzg *ks) {
 // window sizes that are dominated by a smaller table with the same number of additions per point are skipped: GLV c = 14 (2 x 10 windows, 32 GB)
 // against c = 13 (2 x 10, 16 GB); plain c = 15 (18 windows, 116 GB) measured slower than c = 14 (19 windows, 61 GB)
 static bool fb_window_size_skipped(uint32_t c, bool glv) { return glv ? (c == 14) : (c == 15); }
+// bytes of a table of large batches: one window of single-point rows, or the row sets of the point pairs
+static double fb_shared_plan_bytes(const msm_plan &p) { return p.paired ? fb_paired_bytes(p.table_n, p.c) : (double)p.table_n * (double)p.nb * sizeof(g1a); }
 // A resident shared-window table (below) is paid from the same budget: the all-window table gets what it leaves.
 int ensure_fixed_table(kzg_hip_kzg *ks, hipStream_t) {
     if (ks->d_fixed || ks->fixed_plan.c == 0xffffffffu) return KZG_HIP_OK;
     hipStream_t s = ks->fs->stream;
-    const double budget_gb = fb_handle_budget_gb(ks) - (ks->d_shared ? (double)ks->shared_plan.table_n * (double)ks->shared_plan.nb * sizeof(g1a) / 1e9 : 0.0);
+    const double budget_gb = fb_handle_budget_gb(ks) - (ks->d_shared ? fb_shared_plan_bytes(ks->shared_plan) / 1e9 : 0.0);
     if (ks->n_setup < 64) { ks->fixed_plan.c = 0xffffffffu; return KZG_HIP_OK; }   // classic path only
     const bool glv = fb_glv_enabled();
     for (uint32_t c = 16; c >= 5; c--) {
@@ -146,6 +148,36 @@ static uint32_t fb_shared_pick(uint64_t n_setup, double bytes, uint32_t below = 
     return 0;
 }
 static uint32_t fb_plan_additions(const msm_plan &p) { return p.glv ? 2 * p.nwin : p.nwin; }
+// ---------------------------------------------------------------------------------------------------------
+// The PAIRED-POINT table, a third shape of shared_plan (k_msm.hip, fb_pair_index.hpp): entries d0 P_2g + d1 P_2g+1 indexed by the digits of two neighbouring
+// points, W = ceil(128 / c) additions per coefficient.  103.28 GB hold 10-bit digits: 13 additions where the single-point table of that size gives 14.  It is paid
+// from the same budget by the same rules.  In the default mode it is considered only at FB_PAIRED_MIN_BITS digits or wider (the one width that was measured) and
+// only where it gives strictly fewer additions than the single-point table from the same bytes; KZG_HIP_FB_LAYOUT=paired takes it at any budget, the widest of
+// 10 .. 5 bits that fits.  An allocation or build failure falls to the single-point shared table, then on as before.
+// ---------------------------------------------------------------------------------------------------------
+#ifndef FB_PAIRED_MIN_BITS
+#define FB_PAIRED_MIN_BITS 10
+#endif
+static bool fb_paired_forced() { return knobs::fb_layout() == knobs::fb_layout_mode::paired; }
+static uint32_t fb_paired_pick(uint64_t n_setup, double bytes, uint32_t below = FB_PAIRED_MAX_BITS + 1) {
+    for (uint32_t c = below - 1; c >= FB_PAIRED_LOW_BITS; c--)
+        if (fb_paired_bytes(n_setup, c) <= bytes) return c;
+    return 0;
+}
+// whether the paired table of c-bit digits may be built from `bytes` in the current mode
+static bool fb_paired_eligible(uint64_t n_setup, double bytes, uint32_t c) {
+    if (!c) return false;
+    if (fb_paired_forced()) return true;
+    if (knobs::fb_layout() == knobs::fb_layout_mode::shared) return false;   // "shared" keeps meaning the single-point table
+    const uint32_t cs = fb_shared_pick(n_setup, bytes);
+    return c >= FB_PAIRED_MIN_BITS && (!cs || fb_paired_windows(c) < 2 * fb_shared_windows(cs));
+}
+// additions per coefficient of the table of large batches that fb_shared_build would try first from `bytes`; UINT32_MAX: none fits
+static uint32_t fb_shared_additions_at(uint64_t n_setup, double bytes) {
+    const uint32_t cp = fb_paired_pick(n_setup, bytes), cs = fb_shared_pick(n_setup, bytes);
+    if (fb_paired_eligible(n_setup, bytes, cp)) return fb_paired_windows(cp);
+    return cs && !fb_paired_forced() ? 2 * fb_shared_windows(cs) : UINT32_MAX;
+}
 // additions per coefficient of the all-window table that ensure_fixed_table would build from `bytes`; UINT32_MAX: none fits
 static uint32_t fb_windows_additions_at(uint64_t n_setup, double bytes, bool glv) {
     for (uint32_t c = 16; c >= 5; c--) {
@@ -161,9 +193,25 @@ static uint64_t fb_shared_threshold(const kzg_hip_kzg *ks) {
     if (knobs::fb_layout() == knobs::fb_layout_mode::shared) return 1;
     return ks->shared_first ? FB_SHARED_MIN_BATCH_REPLACED : FB_SHARED_MIN_BATCH;
 }
-// builds the largest shared table below 2 * `fewer_than` additions that fits `bytes`; false: none
+// Builds the table of large batches from `bytes`; false: none.  Two loops.  First the paired-point table, widest digits first, while it is eligible in the
+// current mode (fb_paired_eligible) and costs fewer than `fewer_than` additions per coefficient -- KZG_HIP_FB_LAYOUT=paired ignores `fewer_than` and never goes
+// on to the second loop.  Then the single-point table: the widest digits that fit, as long as their 2 W additions stay below `fewer_than`.  In either loop a
+// failed allocation or build moves on to the next narrower width.
 static bool fb_shared_build(kzg_hip_kzg *ks, double bytes, uint32_t fewer_than) {
     hipStream_t s = ks->fs->stream;
+    const bool forced = fb_paired_forced();
+    for (uint32_t c = fb_paired_pick(ks->n_setup, bytes); fb_paired_eligible(ks->n_setup, bytes, c) && (forced || fb_paired_windows(c) < fewer_than); c = fb_paired_pick(ks->n_setup, bytes, c)) {
+        msm_plan p{};
+        p.c = c; p.nwin = fb_paired_windows(c); p.nb = 1u << (c - 1); p.ngroups = 1; p.fixed = 1; p.glv = 1; p.table_n = ks->n_setup; p.paired = 1;
+        g1a *tab = nullptr;
+        if (hipMalloc((void **)&tab, (size_t)fb_paired_table_bytes(ks->n_setup, c, sizeof(g1a))) != hipSuccess) { (void)hipGetLastError(); continue; }   // retry narrower, then single-point
+        hipError_t e = launch_fb_build_paired(s, ks->d_secret_a, ks->n_setup, c, tab);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hipGetLastError(); hipFree(tab); continue; }
+        ks->d_shared = tab; ks->shared_plan = p;
+        return true;
+    }
+    if (forced) return false;
     for (uint32_t c = fb_shared_pick(ks->n_setup, bytes); c && 2 * fb_shared_windows(c) < fewer_than; c = fb_shared_pick(ks->n_setup, bytes, c)) {
         msm_plan p{};
         p.c = c; p.nwin = fb_shared_windows(c); p.nb = 1u << (c - 1); p.ngroups = 1; p.fixed = 1; p.glv = 1; p.table_n = ks->n_setup;
@@ -184,8 +232,8 @@ static int ensure_shared_table(kzg_hip_kzg *ks) {
     const double budget = fb_handle_budget_gb(ks) * 1e9;
     if (ks->d_fixed) {
         if (fb_shared_build(ks, budget - fb_plan_bytes(ks->fixed_plan), fb_plan_additions(ks->fixed_plan))) return KZG_HIP_OK;   // both tables resident
-        const uint32_t c = fb_shared_pick(ks->n_setup, budget);
-        if (!c || 2 * fb_shared_windows(c) >= fb_plan_additions(ks->fixed_plan)) { ks->shared_plan.c = 0xffffffffu; return KZG_HIP_OK; }
+        const uint32_t adds = fb_shared_additions_at(ks->n_setup, budget);
+        if (adds == UINT32_MAX || (!fb_paired_forced() && adds >= fb_plan_additions(ks->fixed_plan))) { ks->shared_plan.c = 0xffffffffu; return KZG_HIP_OK; }
         HIPCHK(hipDeviceSynchronize());                      // walks of the all-window table in flight (as kzg_hip_kzg_set_table_budget_gb)
         HIPCHK(hipFree(ks->d_fixed));
         ks->d_fixed = nullptr; ks->fixed_plan = msm_plan{};
@@ -219,14 +267,15 @@ int commit_rows(kzg_hip_kzg *ks, hipStream_t s, const fr *d_sc, uint64_t n, uint
         share = may_share && !ks->d_fixed && ks->d_shared && knobs::fb_layout() != knobs::fb_layout_mode::windows;   // the remainder of the budget holds no all-window table
     }
     if (share) {
-        // the digit words are 2 W n x 4 bytes per row (0.94 GB for 4096 blobs at W = 7): batches beyond FB_SHARED_CHUNK rows walk in pieces that reuse one
+        // the digit words are 2 W n x 4 bytes per row (0.94 GB for 4096 blobs at W = 7; paired: 2 W n / 2, 0.87 GB at W = 13): batches beyond FB_SHARED_CHUNK rows walk in pieces that reuse one
         // workspace in stream order, and if even that cannot be had the batch takes the all-window (or bucket) path below -- a commitment never fails for lack of HBM
         const uint64_t piece = batch < FB_SHARED_CHUNK ? batch : FB_SHARED_CHUNK;
         dtmp<uint8_t> d_ws(s);
-        if (d_ws.alloc(fb_shared_workspace_bytes(n, piece, ks->shared_plan.c)) == KZG_HIP_OK) {
+        const bool paired = ks->shared_plan.paired != 0;
+        if (d_ws.alloc(paired ? fb_paired_workspace_bytes(n, piece, ks->shared_plan.c) : fb_shared_workspace_bytes(n, piece, ks->shared_plan.c)) == KZG_HIP_OK) {
             const bool projective = to_kilic && ks->projective.load(std::memory_order_relaxed);
             for (uint64_t b0 = 0; b0 < batch; b0 += piece)
-                launch_fb_msm_shared(s, ks->d_shared, ks->shared_plan.c, d_sc + b0 * sc_stride, sc_stride, n, batch - b0 < piece ? batch - b0 : piece, d_ws.p, d_out + b0, to_kilic, projective);
+                (paired ? launch_fb_msm_paired : launch_fb_msm_shared)(s, ks->d_shared, ks->shared_plan.c, d_sc + b0 * sc_stride, sc_stride, n, batch - b0 < piece ? batch - b0 : piece, d_ws.p, d_out + b0, to_kilic, projective);
             HIPCHK(hipGetLastError());
             return KZG_HIP_OK;
         }
@@ -657,7 +706,7 @@ int kzg_hip_kzg_table_info(kzg_hip_kzg *ks, uint32_t *window_bits, uint32_t *win
     if (!ks || !window_bits || !windows || !table_bytes) return KZG_HIP_ERR_BAD_ARG;
     const msm_plan *p = ks->d_fixed ? &ks->fixed_plan : ks->d_shared ? &ks->shared_plan : nullptr;   // the all-window table while one exists, else the shared-window one
     *window_bits = p ? p->c : 0; *windows = p ? p->nwin : 0;
-    *table_bytes = p ? (uint64_t)(ks->d_fixed ? p->nwin : 1) * p->table_n * p->nb * sizeof(g1a) : 0;
+    *table_bytes = !p ? 0 : ks->d_fixed ? (uint64_t)p->nwin * p->table_n * p->nb * sizeof(g1a) : (uint64_t)fb_shared_plan_bytes(*p);
     return KZG_HIP_OK;
 }
 // The reference's G1Point IS a Jacobian triple (bls/bls_kilic.go:30-35) and CommitToPoly / ComputeProofSingle return whatever Z their additions left; this
@@ -673,6 +722,6 @@ int kzg_hip_kzg_set_projective_outputs(kzg_hip_kzg *ks, int on) {
 // mixed additions per coefficient of a commitment on that table: 2 x windows when both GLV halves of a scalar walk it (the default), else windows; 0 without a table
 uint32_t kzg_hip_kzg_table_additions(kzg_hip_kzg *ks) {
     if (!ks || (!ks->d_fixed && !ks->d_shared)) return 0;
-    if (!ks->d_fixed) return 2 * ks->shared_plan.nwin;     // the shared-window table: one entry per window and GLV half
+    if (!ks->d_fixed) return ks->shared_plan.paired ? ks->shared_plan.nwin : 2 * ks->shared_plan.nwin;     // the shared-window table: one entry per window and GLV half; the paired one: half an entry
     return ks->fixed_plan.glv ? 2 * ks->fixed_plan.nwin : ks->fixed_plan.nwin;
 }

@@ -5,6 +5,7 @@
 #include "field.hpp"
 #include "g1.hpp"
 #include "knobs.hpp"
+#include "fb_pair_index.hpp"
 
 namespace kzg {
 
@@ -137,6 +138,7 @@ struct msm_plan {
     uint32_t fixed;    // 1: plan of a fixed-base table (k_fb_*), 0: bucket MSM
     uint32_t glv;      // fixed-base walk: 1 = the table holds ceil(128 / c) windows and both GLV halves of a scalar walk them (k_fb_accumulate_glv)
     uint64_t table_n;  // points per row of the table
+    uint32_t paired;   // shared-window plans only: 1 = the paired-point table (entries indexed by the digits of two neighbouring points, nwin additions per coefficient)
 };
 // the bucket pipeline packs (point index << 2 | half | sign) into 32 bits and counts entries (32 per scalar) in 32 bits: both must fit
 inline bool msm_index_range_ok(const msm_plan &p, uint64_t n) { return n < (1ull << 27) && 2 * p.table_n < (1ull << 30); }
@@ -161,6 +163,13 @@ inline uint32_t fb_shared_windows(uint32_t c) { return (128 + c - 1) / c; }
 size_t fb_shared_workspace_bytes(uint64_t n, uint64_t batch, uint32_t c);
 hipError_t launch_fb_build_shared(hipStream_t s, const g1a *pts, uint64_t n, uint32_t c, g1a *table);
 void launch_fb_msm_shared(hipStream_t s, const g1a *table, uint32_t c, const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, void *workspace, g1j *out,
+                          bool to_kilic, bool projective);
+// the paired-point layout (k_msm.hip, fb_pair_index.hpp): table[g E + idx(d0, d1)] = d0 P_2g + d1 P_2g+1, E = fb_paired_entries(c), W = fb_paired_windows(c)
+// accumulators per blob and W additions per coefficient; digit widths FB_PAIRED_LOW_BITS .. FB_PAIRED_MAX_BITS
+inline double fb_paired_bytes(uint64_t n, uint32_t c) { return (double)fb_paired_table_bytes(n, c, 2 * sizeof(fp)); }
+size_t fb_paired_workspace_bytes(uint64_t n, uint64_t batch, uint32_t c);
+hipError_t launch_fb_build_paired(hipStream_t s, const g1a *pts, uint64_t n, uint32_t c, g1a *table);
+void launch_fb_msm_paired(hipStream_t s, const g1a *table, uint32_t c, const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, void *workspace, g1j *out,
                           bool to_kilic, bool projective);
 
 // out[(b, f, jj)] = scalars[b][f * row + j0 + jj] * P[f * row + j0 + jj] over a fixed-base table of table_n = nfiles * row points

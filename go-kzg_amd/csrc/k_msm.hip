@@ -926,6 +926,141 @@ __global__ __launch_bounds__(256) void k_fb_finish_shared(const fb_partial *part
     quad_horner_finish(partials + (live ? b : 0) * W * blocks_per_blob, W, c, blocks_per_blob, live, role, out + (live ? b : 0), fin);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The PAIRED-POINT layout.  14 additions per coefficient are the floor of tables indexed by one digit of one point.  An entry indexed by the digits of TWO
+// neighbouring points,  T_p[g E + idx(d0, d1)] = d0 P_2g + d1 P_2g+1  (fb_pair_index.hpp: tuples up to a common sign, E = 2 D (D + 1) per pair), consumes 2 c
+// scalar bits per gathered entry: 103 GB are 2048 x 525 312 entries, signed 10-bit digits, 13 windows per GLV half and PAIR = 13 additions per coefficient.
+//   k_fb_build_paired_pass1 : lane (pair, seg) walks S consecutive entries of the pair's row set: within a run (one d0) the next entry is + P_2g+1, at the end of
+//                             a run it restarts from (d0 + 1) P_2g - D P_2g+1.  Every step is a complete addition (g1_madd / g1_add): on a setup with
+//                             P_2g+1 = +-P_2g the running point meets the addend, its negative and infinity in every run.  k_fb_build_pass2 normalises
+//                             (infinity entries become g1a_inf(), which the walk's acc.add skips).
+//   k_fb_digits_paired      : one lane per (blob, pair) splits both scalars once; words at digits[blob][half][w][pair], half 0 is the phi half
+//   k_fb_accumulate_paired  : the walk of k_fb_accumulate_shared with a row base and a word; W = 13 does not divide 64 quads, so a window owns
+//                             LW = floor(256 / W) LANES (19: 247 of 256 live) and the block end sums any lane count per window through LDS
+//   k_fb_finish_shared      : unchanged (W windows of c bits)
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ g1j fb_small_mul(const g1a &b, uint32_t k) {
+    g1j cur = g1_inf();
+    if (!k) return cur;
+#pragma nounroll
+    for (int bit = 31 - __builtin_clz(k); bit >= 0; bit--) {
+        cur = g1_dbl(cur);
+        if ((k >> bit) & 1u) cur = g1_madd(cur, b);
+    }
+    return cur;
+}
+__global__ __launch_bounds__(FB_BLOCK, 2) void k_fb_build_paired_pass1(const g1a *pts, uint64_t n, uint64_t pair0, uint64_t pairs, uint32_t D, uint32_t E, uint32_t S, g1a *table, fp *ztmp) {
+    const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    const uint32_t segs = E / S;
+    if (t >= pairs * segs) return;
+    const uint64_t pair = t / segs; const uint32_t seg = (uint32_t)(t % segs);
+    const uint64_t i0 = 2 * (pair0 + pair);
+    const g1a p0 = pts[i0], p1 = i0 + 1 < n ? pts[i0 + 1] : g1a_inf();
+    int32_t d0, d1;
+    fb_pair_tuple(seg * S, D, d0, d1);
+    g1j base0 = fb_small_mul(p0, (uint32_t)d0);                       // d0 P_2g
+    const g1j low = g1_neg(fb_small_mul(p1, D));                      // -D P_2g+1: where every run but the first starts
+    g1j cur = g1_add(base0, d1 < 0 ? g1_neg(fb_small_mul(p1, (uint32_t)-d1)) : fb_small_mul(p1, (uint32_t)d1));
+    g1a *dst = table + pair * E + (uint64_t)seg * S; fp *zd = ztmp + pair * E + (uint64_t)seg * S;
+#pragma nounroll
+    for (uint32_t e = 0; e < S; e++) {
+        g1a xy; xy.x = cur.x; xy.y = cur.y;
+        dst[e] = xy; zd[e] = cur.z;
+        if (d1 == (int32_t)D) { d0++; d1 = -(int32_t)D; base0 = g1_madd(base0, p0); cur = g1_add(base0, low); }
+        else { d1++; cur = g1_madd(cur, p1); }
+    }
+}
+__global__ __launch_bounds__(256) void k_fb_digits_paired(const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, uint32_t c, uint32_t W, uint32_t *digits) {
+    const uint64_t np = fb_paired_pairs(n);
+    const uint64_t t = blockIdx.x * 256ull + threadIdx.x;
+    if (t >= np * batch) return;
+    const uint64_t blob = t / np, g = t % np;
+    const fr *sc = scalars + blob * sc_stride;
+    const glv_halves h0 = glv_split_signed(from_mont<FrP>(sc[2 * g]));
+    glv_halves h1 = h0;                                    // (defined words; not read without a partner)
+    const bool partner = 2 * g + 1 < n;                    // a coefficient without a partner pairs with digit 0: zero magnitude, no sign
+    if (partner) h1 = glv_split_signed(from_mont<FrP>(sc[2 * g + 1]));
+#pragma unroll
+    for (uint32_t half = 0; half < 2; half++) {
+        uint32_t m0[4], m1[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) { m0[j] = half ? h0.k1[j] : h0.k2[j]; m1[j] = partner ? (half ? h1.k1[j] : h1.k2[j]) : 0u; }
+        fb_pair_recode(m0, (half ? h0.neg1 : h0.neg2) != 0, m1, partner && (half ? h1.neg1 : h1.neg2) != 0, c, W, digits + ((blob * 2 + half) * W) * np + g, np);
+    }
+}
+__global__ __launch_bounds__(FB_ACC_BLOCK, FB_ACC_WAVES) void k_fb_accumulate_paired(const g1a *table, uint64_t E, uint32_t W, uint32_t LW, const uint32_t *digits, uint64_t np,
+                                                                                   uint32_t blocks_per_blob, fb_partial *partials) {
+    __shared__ fb_partial buf[FB_ACC_BLOCK];
+    const uint32_t tid = threadIdx.x, role = tid & 3u, quad = tid >> 2;
+    const uint64_t blob = blockIdx.x / blocks_per_blob; const uint32_t blk = blockIdx.x % blocks_per_blob;
+    const bool live = tid < W * LW;
+    const uint32_t w = live ? tid / LW : 0u;
+    g1x_acc acc; acc.init();
+    if (live) {
+        // lane j of its window takes the pairs (t blocks_per_blob + blk) LW + j; counts differ by one step between lanes, so the crossing below is per lane
+        const uint64_t stride = (uint64_t)blocks_per_blob * LW;
+        const uint64_t i0 = (uint64_t)blk * LW + (tid - w * LW);
+        const uint64_t cnt = i0 < np ? (np - i0 + stride - 1) / stride : 0;
+        const uint32_t *dphi = digits + ((blob * 2) * W + w) * np, *dplain = dphi + (uint64_t)W * np;
+        const uint64_t K = 2 * cnt;
+        if (K) {
+            // software pipeline of k_fb_accumulate_shared: the digit word of step k + 2 and the gather of step k + 1 are issued before the addition of step k
+            uint32_t wc = dphi[i0];
+            g1a qn = table[i0 * E + ((wc & FB_DIGIT_MAG) ? (wc & FB_DIGIT_MAG) - 1 : 0)];
+            uint32_t wn = cnt > 1 ? dphi[i0 + stride] : dplain[i0];
+#pragma nounroll
+            for (uint64_t k = 0; k < K; k++) {
+                const g1a q0 = qn;
+                const uint32_t cur = wc;
+                wc = wn;
+                if (k + 1 < K) {
+                    const uint64_t i1 = i0 + (k + 1 < cnt ? k + 1 : k + 1 - cnt) * stride;
+                    qn = table[i1 * E + ((wc & FB_DIGIT_MAG) ? (wc & FB_DIGIT_MAG) - 1 : 0)];
+                }
+                if (k + 2 < K) wn = k + 2 < cnt ? dphi[i0 + (k + 2) * stride] : dplain[i0 + (k + 2 - cnt) * stride];
+                if (k == cnt && !acc.inf) acc.v.x = mulq(acc.v.x, unpackq(glv_beta()));   // the lane crosses into its plain digits: map the phi sum
+                if (cur & FB_DIGIT_MAG) {
+                    g1a q = q0;
+                    if (cur >> 31) q.y = neg<FpP>(q.y);
+                    acc.add(q);                            // (an infinity entry -- d0 P_2g + d1 P_2g+1 = 0 on a setup with dependent neighbours -- is skipped there)
+                }
+            }
+        }
+    }
+    // block end: W sums over LW lanes each, any LW.  Every lane leaves its accumulator in LDS; QW = floor(64 / W) quads per window each sum ceil(LW / QW) of the
+    // window's accumulators (quad-cooperative additions; every quad runs the same chain, idle ones on empty operands), then the window's first quad joins the
+    // QW quad sums: 5 + 3 additions of ~6 us at W = 13 against a workgroup life of milliseconds.
+    if (acc.inf) acc.v = g1xq_from_affine(g1a_inf());      // defined limbs in empty accumulators (their additions are computed and dropped)
+    fb_partial_store(buf[tid], acc);
+    __syncthreads();
+    const uint32_t QW = 64 / W, per = (LW + QW - 1) / QW;
+    const bool qlive = quad < W * QW;                      // (quad-uniform)
+    const uint32_t qw = qlive ? quad / QW : 0u, qj = quad - qw * QW;
+    g1x_acc sum; sum.init();
+    sum.v = g1xq_from_affine(g1a_inf());
+#pragma nounroll
+    for (uint32_t j = 0; j < per; j++) {
+        const uint32_t l = qj * per + j;
+        const bool have = qlive && l < LW;
+        const fb_partial &src = buf[have ? qw * LW + l : tid];
+        g1xq v; fb_partial_load(src, v);
+        quad_tree_add(sum, v, !have || src.inf != 0, role);
+    }
+    __syncthreads();                                       // every quad has read its lanes: slots 0 .. 63 now take the quad sums
+    if (role == 0) fb_partial_store(buf[quad], sum);
+    __syncthreads();
+    const uint32_t base = qlive ? qw * QW : quad;          // idle quads chain over their own (empty) column
+    g1x_acc tot;
+    fb_partial_load(buf[base], tot.v); tot.inf = buf[base].inf != 0;
+#pragma nounroll
+    for (uint32_t j = 1; j < QW; j++) {
+        const fb_partial &src = buf[qlive ? base + j : quad];
+        g1xq v; fb_partial_load(src, v);
+        quad_tree_add(tot, v, !qlive || src.inf != 0, role);
+    }
+    if (qlive && quad == base && role == 0) fb_partial_store(partials[(blob * W + qw) * blocks_per_blob + blk], tot);
+}
+
 // One fixed-base product added into an accumulator: the walk of point i's rows with the signed c-bit digits of a scalar (standard form), sign sg folded in.
 //   GLV = false: the plain layout, nwin windows over the whole scalar (phi is ignored, one call per term);
 //   GLV = true : the table holds ceil(128 / c) windows; the call walks ONE half of the split scalar -- phi ? |k2| : |k1| -- so a caller sums the phi halves of all
@@ -1232,6 +1367,58 @@ hipError_t launch_fb_build_shared(hipStream_t s, const g1a *pts, uint64_t n, uin
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+// The paired-point walk (k_fb_accumulate_paired): a window owns LW = floor(256 / W) lanes; workgroups per blob as above, but never more than give every
+// lane of a window a pair
+static uint32_t fb_paired_blocks_per_blob(uint64_t n, uint64_t batch, uint32_t W) {
+    const uint32_t LW = FB_ACC_BLOCK / W;
+    const uint64_t np = fb_paired_pairs(n), maxb = (np + LW - 1) / LW;
+    const uint64_t bpb = fb_blocks_per_blob(2 * n, batch);
+    return (uint32_t)(bpb > maxb ? maxb : bpb);
+}
+static size_t fb_paired_digit_bytes(uint64_t n, uint64_t batch, uint32_t W) { return (((size_t)batch * 2 * W * fb_paired_pairs(n) * sizeof(uint32_t)) + 15) / 16 * 16; }
+size_t fb_paired_workspace_bytes(uint64_t n, uint64_t batch, uint32_t c) {
+    const uint32_t W = fb_paired_windows(c);
+    return fb_paired_digit_bytes(n, batch, W) + (((size_t)fb_paired_blocks_per_blob(n, batch, W) * W * batch * sizeof(fb_partial)) + 15) / 16 * 16;
+}
+// table[g E + idx(d0, d1)] = d0 P_2g + d1 P_2g+1 (fb_pair_index.hpp), 5 <= c <= 10: the digit pre-pass, the walk, the Horner finish of the shared-window walk
+void launch_fb_msm_paired(hipStream_t s, const g1a *table, uint32_t c, const fr *scalars, uint64_t sc_stride, uint64_t n, uint64_t batch, void *workspace, g1j *out,
+                          bool to_kilic, bool projective) {
+    if (!batch) return;
+    const uint32_t W = fb_paired_windows(c), LW = FB_ACC_BLOCK / W;
+    const uint64_t np = fb_paired_pairs(n);
+    const uint32_t bpb = fb_paired_blocks_per_blob(n, batch, W);
+    uint32_t *digits = (uint32_t *)workspace;
+    fb_partial *partials = (fb_partial *)((uint8_t *)workspace + fb_paired_digit_bytes(n, batch, W));
+    hipLaunchKernelGGL(k_fb_digits_paired, dim3((uint32_t)((np * batch + 255) / 256)), dim3(256), 0, s, scalars, sc_stride, n, batch, c, W, digits);
+    prof_begin(s, "fb_accumulate");
+    hipLaunchKernelGGL(k_fb_accumulate_paired, dim3((uint32_t)(batch * bpb)), dim3(FB_ACC_BLOCK), 0, s, table, fb_paired_entries(c), W, LW, digits, np, bpb, partials);
+    prof_end(s, "fb_accumulate");
+    hipLaunchKernelGGL(k_fb_finish_shared, dim3((uint32_t)((batch + 63) / 64)), dim3(256), 0, s, (const fb_partial *)partials, c, W, bpb, batch, out,
+                       (to_kilic ? 1 : 0) | (projective ? 2 : 0));
+}
+// the paired-point table of `n` points, in slices of pairs so that the Z and prefix temporaries stay near 2 x 1 GiB at every digit width
+hipError_t launch_fb_build_paired(hipStream_t s, const g1a *pts, uint64_t n, uint32_t c, g1a *table) {
+    if (c < FB_PAIRED_LOW_BITS || c > FB_PAIRED_MAX_BITS) return hipErrorInvalidValue;
+    const uint32_t D = 1u << (c - 1);
+    const uint64_t E = fb_paired_entries(c), pairs = fb_paired_pairs(n);
+    uint64_t slice = (1ull << 30) / (E * sizeof(fp));
+    if (slice < 1) slice = 1;
+    if (slice > pairs) slice = pairs;
+    fp *ztmp = nullptr, *ptmp = nullptr;
+    hipError_t e;
+    if ((e = hipMallocAsync((void **)&ztmp, slice * E * sizeof(fp), s)) != hipSuccess) return e;
+    if ((e = hipMallocAsync((void **)&ptmp, slice * E * sizeof(fp), s)) != hipSuccess) { hipFreeAsync(ztmp, s); return e; }
+    for (uint64_t g0 = 0; g0 < pairs; g0 += slice) {
+        const uint64_t cnt = pairs - g0 < slice ? pairs - g0 : slice;
+        uint32_t S = 2 * D;                                  // segment length (a power of two, so it divides E = 2 D (D + 1)): split until the slice fills the device
+        while (S > 64 && cnt * (E / S) < (1ull << 17)) S >>= 1;
+        dim3 g((uint32_t)((cnt * (E / S) + FB_BLOCK - 1) / FB_BLOCK)), b(FB_BLOCK);
+        hipLaunchKernelGGL(k_fb_build_paired_pass1, g, b, 0, s, pts, n, g0, cnt, D, (uint32_t)E, S, table + g0 * E, ztmp);
+        hipLaunchKernelGGL(k_fb_build_pass2, g, b, 0, s, cnt, (uint32_t)E, S, table + g0 * E, ztmp, ptmp);
+    }
+    hipFreeAsync(ztmp, s); hipFreeAsync(ptmp, s);
+    return hipGetLastError();
 }
 // builds the table for `n` affine points: rows (2^(c w) P_i) first, then all multiples window-slab by window-slab
 hipError_t launch_fb_build(hipStream_t s, const g1a *pts, uint64_t n, uint32_t c, uint32_t nwin, g1a *table) {

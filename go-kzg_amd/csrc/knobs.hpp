@@ -33,7 +33,7 @@ enum class transcript_mode { by_count, host, device };
 enum class pairing_mode { by_count, lane, wave };
 enum class combine_mode { by_count, never, always };
 enum class transport_mode { by_devices, rccl, host, peer };
-enum class fb_layout_mode { by_batch, windows, shared };
+enum class fb_layout_mode { by_batch, windows, shared, paired };
 struct opt_gb { bool set; double gb; };   // a table budget: unset leaves the size to the caller's policy
 
 // ---- grammar
@@ -95,7 +95,7 @@ KZG_KNOB_ONCE(int, msm_seg, "KZG_HIP_MSM_SEG", e ? atoi(e) : -1)                
 KZG_KNOB_PER_CALL(transcript_mode, eth_transcript, "KZG_HIP_ETH_TRANSCRIPT", is(e, "host") ? transcript_mode::host : is(e, "device") ? transcript_mode::device : transcript_mode::by_count)   // where the aggregate verifier and the batched aggregate prover hash
 KZG_KNOB_PER_CALL(pairing_mode, pairing, "KZG_HIP_PAIRING", is(e, "lane") ? pairing_mode::lane : is(e, "wave") ? pairing_mode::wave : pairing_mode::by_count)   // the kernel of every pairing check: one lane or one wavefront per check (launch_pairing_check; tests, A/B runs)
 KZG_KNOB_PER_CALL(combine_mode, verify_combine, "KZG_HIP_VERIFY_COMBINE", is(e, "never") ? combine_mode::never : is(e, "always") ? combine_mode::always : combine_mode::by_count)   // the _combined proof checks: per-row checks or one check per group of rows at every count (capi_verify.hip; tests, A/B runs)
-KZG_KNOB_PER_CALL(fb_layout_mode, fb_layout, "KZG_HIP_FB_LAYOUT", is(e, "windows") ? fb_layout_mode::windows : is(e, "shared") ? fb_layout_mode::shared : fb_layout_mode::by_batch)   // commitment tables: "windows" never builds or walks the shared-window table, "shared" walks it at every batch size; anything else ("auto"): large batches only (capi_kzg.hip)
+KZG_KNOB_PER_CALL(fb_layout_mode, fb_layout, "KZG_HIP_FB_LAYOUT", is(e, "windows") ? fb_layout_mode::windows : is(e, "shared") ? fb_layout_mode::shared : is(e, "paired") ? fb_layout_mode::paired : fb_layout_mode::by_batch)   // commitment tables: "windows" never builds or walks a table of large batches, "shared" walks the single-point shared-window table at every batch size, "paired" makes the table of large batches the paired-point one at any budget; anything else ("auto"): large batches only, the layout with fewer additions (capi_kzg.hip)
 KZG_KNOB_PER_CALL(int, multi_fft, "KZG_HIP_MULTI_FFT", !e ? -1 : is(e, "sharded") ? 1 : 0)                                                   // -1 the handle's policy; "sharded" 1; ANY other value gathers (0)
 KZG_KNOB_PER_HANDLE(transport_mode, multi_transport, "KZG_HIP_MULTI_TRANSPORT", !e ? transport_mode::by_devices : is(e, "rccl") ? transport_mode::rccl : is(e, "host") ? transport_mode::host : transport_mode::peer)   // any other value: peer copies, RCCL is not bound
 KZG_KNOB_PER_HANDLE(unsigned, multi_fault, "KZG_HIP_MULTI_FAULT", multi_fault_of(e))                                                        // tests: a comma-separated list of legs of the exchange that fail, FAULT_* above

@@ -478,7 +478,10 @@ int kzg_hip_multi_da_using_fk20_multi(kzg_hip_multi_fk20m *fk, const void *poly_
  * Batches of 2048 rows and more (kzg_hip_commit_to_poly_batch, _dev) walk a second, shared-window table d P_i paid from the same budget (one accumulator per window, joined
  * per blob: 19-bit digits, 7 windows, 14 additions from the same 103 GB); where the budget cannot hold both and the shared table needs fewer additions it replaces the
  * all-window table, and later small calls get the all-window table the remainder affords.  These two calls describe the all-window table while one exists, otherwise the
- * shared one: window bits, windows per GLV half, bytes; 2 x windows additions.  KZG_HIP_FB_LAYOUT=windows keeps every batch on the all-window table. */
+ * shared one: window bits, windows per GLV half, bytes; 2 x windows additions.  Where the budget holds the paired-point form of that table with 10-bit digits and
+ * it needs fewer additions than single-point digits from the same bytes (the default budget: entries d0 P_2g + d1 P_2g+1, 13 windows, 103 280 541 696 bytes), large
+ * batches walk that one instead: one gathered entry serves a digit of two neighbouring coefficients, so the calls report (10, 13, bytes) and `windows` additions, 13.
+ * KZG_HIP_FB_LAYOUT=windows keeps every batch on the all-window table. */
 int kzg_hip_kzg_table_info(kzg_hip_kzg *ks, uint32_t *window_bits, uint32_t *windows, uint64_t *table_bytes);
 uint32_t kzg_hip_kzg_table_additions(kzg_hip_kzg *ks);
 /* Projective outputs (off by default).  The reference's G1Point is a Jacobian triple and CommitToPoly / ComputeProofSingle return it with whatever Z the

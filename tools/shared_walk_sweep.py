@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Crossovers of the shared-window walk (FB_SHARED_MIN_BATCH, FB_SHARED_MIN_BATCH_REPLACED in go-kzg_amd/csrc/capi_kzg.hip): ms per
-kzg_hip_commit_to_poly_batch_dev step on device-resident blobs, one process, three handles on the 4096-point setup:
+kzg_hip_commit_to_poly_batch_dev step on device-resident blobs, one process, four handles on the 4096-point setup:
     windows16 : the all-window table of the default budget (c = 16, 103 GB), KZG_HIP_FB_LAYOUT=windows -- the walk every batch took before
     windows11 : the all-window table a handle keeps beside a shared table of the whole default budget (c = 11, 4.8 GB)
-    shared    : the shared-window table of the default budget (c = 19, 103 GB), forced at every batch size
-Prints median and spread (max - min) of the timed steps per batch size and checks that the three agree on the commitments.
+    shared    : the single-point shared-window table of the default budget (c = 19, 103 GB), forced at every batch size
+    paired    : the paired-point table of the default budget (10-bit digits of two neighbouring points, 103 GB, 13 additions), forced at every batch size
+Prints median and spread (max - min) of the timed steps per batch size and checks that the four agree on the commitments.
 usage: python tools/shared_walk_sweep.py [steps]"""
 import os, sys, time
 import numpy as np
@@ -42,7 +43,8 @@ def run(ks, env, B):
 
 
 legs = (("windows16", 110.0, {"KZG_HIP_FB_LAYOUT": "windows"}), ("windows11", 6.0, {"KZG_HIP_FB_LAYOUT": "windows"}),
-        ("shared", 110.0, {"KZG_HIP_FB_SHARED_MIN_BATCH": "1"}))
+        ("shared", 110.0, {"KZG_HIP_FB_LAYOUT": "shared", "KZG_HIP_FB_SHARED_MIN_BATCH": "1"}),
+        ("paired", 110.0, {"KZG_HIP_FB_LAYOUT": "paired", "KZG_HIP_FB_SHARED_MIN_BATCH": "1"}))
 res, outs = {}, {}
 for name, gb, env in legs:
     ks = kz.KZGSettings(fs, setup)
@@ -55,9 +57,9 @@ for name, gb, env in legs:
         res[name, B] = (med, spread)
         outs[name, B] = out
     ks.close()
-print("| blobs | windows16 ms (spread) | windows11 ms (spread) | shared ms (spread) | shared / windows16 | shared / windows11 |")
-print("|---|---|---|---|---|---|")
+print("| blobs | windows16 ms (spread) | windows11 ms (spread) | shared ms (spread) | paired ms (spread) | shared / windows16 | shared / windows11 | paired / shared |")
+print("|---|---|---|---|---|---|---|---|")
 for B in sizes:
-    a, b, c = res["windows16", B], res["windows11", B], res["shared", B]
-    assert np.array_equal(outs["windows16", B], outs["shared", B]) and np.array_equal(outs["windows11", B], outs["shared", B]), B
-    print("| %d | %.3f (%.3f) | %.3f (%.3f) | %.3f (%.3f) | %.3f | %.3f |" % (B, a[0], a[1], b[0], b[1], c[0], c[1], c[0] / a[0], c[0] / b[0]), flush=True)
+    a, b, c, d = res["windows16", B], res["windows11", B], res["shared", B], res["paired", B]
+    assert np.array_equal(outs["windows16", B], outs["shared", B]) and np.array_equal(outs["windows11", B], outs["shared", B]) and np.array_equal(outs["paired", B], outs["shared", B]), B
+    print("| %d | %.3f (%.3f) | %.3f (%.3f) | %.3f (%.3f) | %.3f (%.3f) | %.3f | %.3f | %.3f |" % (B, a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1], c[0] / a[0], c[0] / b[0], d[0] / c[0]), flush=True)
